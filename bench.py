@@ -1,8 +1,13 @@
 """Benchmark: CycleGAN train-step images/sec at 512x512, bs=8 per GPU (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the
+legs that take runs of their own (today: cpu_baseline).  --dump-outputs DIR writes what the last
+timed step returned and left behind (see dump_outputs) as DIR/<name>.npy; the inputs and the
+initial weights are seeded, so two builds run with the same arguments compare file for file.
 
 A step is one full pass of modules/trainer.py:463-525 (G step with all nine loss terms and
 its Adam, D_A step, D_B step) on the fused HIP path, over one synthetic batch of 8 slices per
@@ -21,8 +26,8 @@ measured live with HIP events on the launch stream over the timed steps; FLOPs a
 (2*pixels*256*256*9 per launch).  Peak: 157.3 TFLOP/s for f32 (gfx950 f32 MFMA, dense); the dense
 fp16/bf16 MFMA peak (2.5 PF) divided by the products per fragment pair in the split modes (f16x3:
 3 -> 838.9 TFLOP/s of fp32 work; bf16x6: 6 -> 419.5).
-cpu_baseline: the oracle (oracle/ref_torch.py, the CPU restatement of the reference step)
-timed on this host on a bounded sample (one 512x512 slice, 9 blocks, one step).
+cpu_baseline (--full only): the oracle (oracle/ref_torch.py, the CPU restatement of the reference
+step) timed on the host's cores on a bounded sample (one 512x512 slice, 9 blocks, one step).
 """
 from __future__ import annotations
 
@@ -86,7 +91,7 @@ def cpu_baseline(img, blocks, cin, threads):
     """BASELINE.md section 3 on this host's cores: the oracle's CPU step at BASELINE config 1 (128x128,
     bs 2, 1 residual block) and at the metric's shape (512x512, bs 1, 9 blocks), 3 untimed warm-up
     steps each, median of the timed steps.  ``value`` is the 512x512 rate (same slice shape as the
-    GPU metric); the 512x512 sample is 3 timed steps to keep the default bench within minutes."""
+    GPU metric); the 512x512 sample is 3 timed steps to keep the --full bench within minutes."""
     sys.path.insert(0, ROOT)
     torch.set_num_threads(threads)
     c1 = _cpu_steps(128, 2, 1, cin, 3, 10)
@@ -115,6 +120,38 @@ def all_finite(tensors) -> bool:
     return bool(torch.cat(flags).all().item()) if flags else True
 
 
+DUMP_MAX_ELEMS = 1 << 21  # per array: 8 MB of float32
+DUMP_MAX_BYTES = 64 << 20  # all arrays of one run
+
+
+def _dump_sample(t):
+    """``t`` flattened as float32 on the host; an array of more than DUMP_MAX_ELEMS elements is cut to
+    a fixed sample of that many (indices drawn with replacement from a CPU generator seeded with the
+    array's length, so the same positions in every run and every build)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(flat.numel())
+        idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g)
+        return flat[idx.to(flat.device)].float().cpu().numpy()
+    return t.detach().float().cpu().numpy()
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``arrays`` (name -> tensor) as out_dir/<name>.npy in float32: what the last timed step
+    returned (the loss terms, or the Generator's output) and the state it left to its caller (each
+    optimizer's flat parameter buffer after the step's Adam updates; parameter gradients for
+    --workload g_a2b), large ones as the fixed sample of _dump_sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = _dump_sample(t)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _pmc_record(mode):
     """HBM bytes per launch (2*FETCH_SIZE + WRITE_SIZE, gfx950 FETCH correction) and MFMA-busy of the
     dominant kernel from the committed rocprofv3 PMC passes (profiles/pmc_resconv_MODE.json, written
@@ -139,7 +176,13 @@ def main():
     ap.add_argument("--img", type=int, default=512)
     ap.add_argument("--blocks", type=int, default=9)
     ap.add_argument("--cin", type=int, default=3, help="1 + masks (soft tissue: 3, lung: 2)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure, each a run of its own: cpu_baseline "
+                         "(the oracle's CPU step, one GPU, --workload step)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs and the parameters it left "
+                         "as DIR/<name>.npy (float32; large arrays as a fixed seeded sample)")
     ap.add_argument("--mma", default="f16x3", choices=["f32", "bf16", "bf16x3", "bf16x6", "f16x3", "f16"],
                     help="MFMA operand mode of the conv passes: f16x3 = power-of-two scaled hi/lo fp16 split, "
                          "three products, fp32-class (default; error <= the exact-f32 path's, "
@@ -265,6 +308,23 @@ def main():
         torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN)
         replicas_ok = bool(ok.item()) if flats else None
 
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        many = len(outs) > 1
+        for i, o in enumerate(outs):
+            pre = f"m{i}_" if many else ""
+            for k, v in (o.items() if isinstance(o, dict) else [("out", o)]):
+                arrays[pre + k] = v
+        if args.workload == "g_a2b" and not groups:
+            arrays["params"] = torch.cat([p_.detach().reshape(-1) for p_ in G.parameters()])
+            arrays["param_grads"] = torch.cat([p_.grad.reshape(-1) for p_ in G.parameters()])
+        else:
+            for i, sm in enumerate(sysms_all):
+                pre = f"m{i}_" if len(sysms_all) > 1 else ""
+                for nm, opt in zip(("G", "D_A", "D_B"), sm.optimizers):
+                    arrays[f"{pre}params_{nm}"] = opt.flat_p
+        dump_outputs(args.dump_outputs, arrays)
+
     if rank == 0:
         # img/s over the median step; the mean over the whole timed loop beside it
         value = world * models * args.batch / (med_ms * 1e-3)
@@ -332,7 +392,8 @@ def main():
                 "gflop_per_launch": round(flop_launch / 1e9, 3),
             },
         }
-        if world == 1 and finite and not args.no_cpu_baseline and not args.dual and args.workload == "step":
+        if (args.full and world == 1 and finite and not args.no_cpu_baseline and not args.dual
+                and args.workload == "step"):
             threads = min(16, os.cpu_count() or 1)
             rec["cpu_baseline"] = cpu_baseline(args.img, args.blocks, args.cin, threads)
         print(json.dumps(rec), flush=True)

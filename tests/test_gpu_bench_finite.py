@@ -39,6 +39,45 @@ def test_all_finite_helper_cpu():
     assert not bench.all_finite([torch.tensor(float("inf"))])
 
 
+def test_dump_outputs_helper_cpu(tmp_path):
+    """dump_outputs writes float32 .npy files; an array above the per-array cap becomes the same fixed
+    sample of it in every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 5, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": torch.tensor(1.5), "big": big, "m": torch.ones(2, 3)})
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "big", "m")}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].shape == () and float(a["loss"]) == 1.5 and a["m"].shape == (2, 3)
+    assert a["big"].shape == (bench.DUMP_MAX_ELEMS,) and len(np.unique(a["big"])) > bench.DUMP_MAX_ELEMS // 2
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) has no cpu_baseline leg; --dump-outputs writes the last step's loss terms
+    and the three optimizers' parameters, and the line keeps its headline fields."""
+    import numpy as np
+    args = [a for a in SMALL if a != "--no-cpu-baseline"]
+    env = dict(os.environ, PYTHONUNBUFFERED="1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, "--dump-outputs",
+                        str(tmp_path / "out")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = _record(r.stdout)
+    assert "cpu_baseline" not in rec and rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 2 / (rec["ms_per_step"] * 1e-3)) <= 1e-2 * rec["value"]
+    names = {p.name for p in (tmp_path / "out").iterdir()}
+    assert {"loss_G.npy", "params_G.npy", "params_D_A.npy", "params_D_B.npy"} <= names, names
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / "out" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total <= 64 << 20
+
+
 @pytest.mark.gpu
 def test_bench_reports_finite_step():
     r = _bench()
