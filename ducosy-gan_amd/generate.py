@@ -11,7 +11,10 @@ Differences from the reference, all deliberate:
     checkpoints that train.py writes); a mask-conditioned Generator gets the anatomical masks
     of the NCCT slice in its training order (soft tissue: bone, mediastinum; lung: lung;
     modules/argmanager.py) from the GPU mask kernel, as the training data pipeline built them;
-  * checkpoints are read with torch.load(weights_only=True).
+  * checkpoints are read with torch.load(weights_only=True);
+  * --postprocess_device cuda runs the synthesis stage's HU-range merge and volume smoothing on
+    the GPU (modules/postprocess_gpu.py, csrc/volume.hip) instead of scipy on the host: one
+    upload of the three series, one download of the int16 volume, identical output files.
 DICOM reading/writing uses modules/dicom.py (pydicom is not installed in this image).
 """
 import argparse
@@ -28,7 +31,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from modules.inference import (hu_from_stored, normalise_hu, smooth_volume, stored_from_output,  # noqa: E402
-                               synthesize, translate_slices)
+                               synthesize, synthesize_volume, translate_slices)
 from modules.model import Generator  # noqa: E402
 
 
@@ -129,6 +132,7 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
     output/{dataset}/{patient}/{idx:04d}.dcm."""
     from modules import dicom
     sa, la = _model_args(args, soft_tissue_args, lung_args)
+    post_dev = f"cuda:{args.gpu_id}" if getattr(args, "postprocess_device", "cpu") == "cuda" else None
     for dataset_name in args.dataset_names:
         working_dir = os.path.join(args.working_dir_root, dataset_name)
         output_dir = os.path.join(args.output_dir_root, dataset_name)
@@ -137,14 +141,25 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
             if not all(lists) or len({len(x) for x in lists}) != 1:
                 print(f"Skipping {patient_dir}: missing or mismatched slices")
                 continue
-            merged = []
+            merged, series, rescale = [], [], []
             for rp, sp, lp in zip(*lists):
                 raw, st, lg = dicom.dcmread(rp), dicom.dcmread(sp), dicom.dcmread(lp)
+                if post_dev is not None:
+                    series.append((raw.pixel_array, st.pixel_array, lg.pixel_array))
+                    rescale.append((getattr(raw, "RescaleSlope", 1), getattr(raw, "RescaleIntercept", 0)))
+                    continue
                 raw_hu = hu_from_stored(raw.pixel_array, getattr(raw, "RescaleSlope", 1),
                                         getattr(raw, "RescaleIntercept", 0))
                 merged.append(synthesize(raw.pixel_array, raw_hu, st.pixel_array, lg.pixel_array,
                                          (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max)))
-            vol = smooth_volume(merged)
+            if post_dev is not None:
+                raw_v, soft_v, lung_v = (np.stack(x) for x in zip(*series))
+                on_dev = synthesize_volume(raw_v, [a for a, _ in rescale], [b for _, b in rescale], soft_v, lung_v,
+                                           (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max), device=post_dev,
+                                           keep_on_device=True)
+                vol = smooth_volume(on_dev, device=post_dev)
+            else:
+                vol = smooth_volume(merged)
             out_base = os.path.join(output_dir, os.path.basename(patient_dir))
             os.makedirs(out_base, exist_ok=True)
             for idx, sp in enumerate(lists[1]):
@@ -179,6 +194,8 @@ def get_args(argv=None):
     p.add_argument("--lung_hu_min", type=int, default=-1000)
     p.add_argument("--lung_hu_max", type=int, default=-150)
     p.add_argument("--skip_convert", action="store_true", help="only run the synthesis stage")
+    p.add_argument("--postprocess_device", choices=["cpu", "cuda"], default="cpu",
+                   help="where the synthesis stage merges and smooths the volume (cuda: cuda:{gpu_id})")
     return p.parse_args(argv)
 
 

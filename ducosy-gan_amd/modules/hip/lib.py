@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p, c_char_p
+from ctypes import POINTER, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p, c_char_p
 
 PKG_ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", ".."))
 LIB_PATH = os.environ.get("DUCOSY_HIP_LIB", os.path.join(PKG_ROOT, "lib", "libducosy_hip.so"))
@@ -17,6 +17,8 @@ ACT_NONE, ACT_AFFINE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3, 4
 MMA_F32, MMA_BF16, MMA_BF16X3, MMA_BF16X6, MMA_F16X3, MMA_F16 = 0, 1, 3, 6, 7, 8
 RANGE_PARTS = 512  # DCS_RANGE_PARTS: partial maxima of an f16x3 operand's range record
 KORDER_TAP, KORDER_SLICE, PACK_KSLICE = 0, 1, 8
+VOL_F32, VOL_F64, VOL_I16, VOL_U16 = 0, 1, 2, 3  # DCS_VOL_* dtypes
+VOL_MAX_RADIUS, VOL_MAX_MEDIAN, VOL_MINMAX_PARTS = 16, 9, 1024
 
 
 class ConvDesc(ctypes.Structure):
@@ -168,6 +170,14 @@ SIGNATURES = {
                                  P, P, P]),
     "dcs_masks_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "dcs_anatomical_masks": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, c_size_t, P]),
+    "dcs_vol_gauss1d": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), P]),
+    "dcs_vol_median_z": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    "dcs_vol_kalman_z": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "dcs_vol_minmax": (c_int, [P, c_int64, P, P, P]),
+    "dcs_vol_unsharp_finish": (c_int, [P, c_int, P, P, P, P, c_int64, c_double, c_double, c_float, P, P]),
+    "dcs_vol_finish": (c_int, [P, c_int, P, c_int64, c_float, P, P]),
+    "dcs_vol_merge": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                              P, P, P]),
 }
 
 

@@ -79,12 +79,57 @@ def synthesize(raw_stored: np.ndarray, raw_hu: np.ndarray, soft_stored: np.ndarr
     return merged
 
 
-def smooth_volume(volume: Iterable[np.ndarray]) -> np.ndarray:
+def synthesize_volume(raw_stored, slopes, intercepts, soft_stored, lung_stored, soft_range: Tuple[float, float],
+                      lung_range: Tuple[float, float], device=None, keep_on_device: bool = False):
+    """``synthesize`` over a whole series: [D,H,W] stored values (int16 or uint16) of the NCCT
+    and the two translations, one rescale slope / intercept per slice -> merged stored values.
+    device=None: the per-slice host code.  With a device the merge runs in one kernel there
+    (modules/hip/volume.py); keep_on_device=True then returns the merged values as a float32
+    device tensor, the input of ``smooth_volume(..., device=...)``, instead of downloading."""
+    raw = np.asarray(raw_stored)
+    if device is None:
+        return np.stack([synthesize(r, hu_from_stored(r, a, b), s, g, soft_range, lung_range)
+                         for r, a, b, s, g in zip(raw, slopes, intercepts, np.asarray(soft_stored),
+                                                  np.asarray(lung_stored))])
+    from .hip import volume as V
+    if raw.dtype not in (np.int16, np.uint16):
+        raise TypeError(f"synthesize_volume: stored dtype {raw.dtype} (int16 or uint16 expected)")
+    dev = torch.device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=raw.dtype).view(np.int16)).to(dev)
+    f32 = lambda v: torch.tensor([float(x) for x in v], dtype=torch.float32)
+    with torch.cuda.device(dev):
+        out, f = V.merge_hu_ranges(up(raw), up(soft_stored), up(lung_stored), f32(slopes), f32(intercepts),
+                                   soft_range, lung_range, unsigned=raw.dtype == np.uint16,
+                                   want_stored=not keep_on_device, want_f32=keep_on_device)
+        return f if keep_on_device else out.cpu().numpy().view(raw.dtype)
+
+
+SMOOTH_KW = dict(method="gaussian3d", sigma_z=0.7, sigma_xy=0.05, enhance_sharpness=True, sharpen_amount=1.7,
+                 sharpen_radius=1.2)  # generate.py:251-253
+
+
+def smooth_volume_device(vol: torch.Tensor) -> torch.Tensor:
+    """``smooth_volume`` of a float32 [D,H,W] device tensor, result left on the device (int16)."""
+    from .hip import volume as V
+    from .postprocess_gpu import postprocess_ct_volume_device
+    with torch.cuda.device(vol.device):
+        return postprocess_ct_volume_device(V.gaussian_filter1d(vol, 0.8, 0), **SMOOTH_KW)
+
+
+def smooth_volume(volume: Iterable[np.ndarray], device=None) -> np.ndarray:
     """generate.py:246-254: z Gaussian (sigma 0.8) of the merged stored-value volume, then
     modules/postprocess.py's 'gaussian3d' (sigma_z 0.7, sigma_xy 0.05) with sharpening (1.7 /
-    1.2); voxels >= 750 keep their value; int16 out."""
+    1.2); voxels >= 750 keep their value; int16 out.  device=None runs on the host (scipy); with
+    a device the same arithmetic runs on the volume kernels there, bit-identical
+    (modules/postprocess_gpu.py); ``volume`` may then be a float32 device tensor."""
+    if device is not None:
+        dev = torch.device(device)
+        if isinstance(volume, torch.Tensor):
+            vol = volume.to(device=dev, dtype=torch.float32)
+        else:
+            vol = torch.from_numpy(np.asarray(volume, dtype=np.float32)).to(dev)
+        return smooth_volume_device(vol).cpu().numpy()
     from scipy.ndimage import gaussian_filter1d
     from .postprocess import postprocess_ct_volume
     vol = gaussian_filter1d(np.asarray(volume, dtype=np.float32), sigma=0.8, axis=0)
-    return postprocess_ct_volume(vol, method="gaussian3d", sigma_z=0.7, sigma_xy=0.05, enhance_sharpness=True,
-                                 sharpen_amount=1.7, sharpen_radius=1.2)
+    return postprocess_ct_volume(vol, **SMOOTH_KW)

@@ -597,6 +597,52 @@ int dcs_anatomical_masks(const float* hu, const uint8_t* lung_in, int N, int H, 
                          const int32_t* iparams, const int32_t* chan, int nout, float* out, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* ---- volume post-processing of the synthesis stage (modules/postprocess.py:6-301,
+ *      generate.py:212-254) ----
+ * Dense [D][H][W] device volumes, x fastest.  Every entry point checks its arguments on the
+ * host before any launch (null pointers, D/H/W <= 0, radius, kernel size, axis, dtype) and
+ * returns DCS_E_INVALID on a bad call.  Results are bit-identical to scipy / numpy on the host:
+ * double accumulation in the host's operation order, no fused multiply-add. */
+#define DCS_VOL_F32 0
+#define DCS_VOL_F64 1
+#define DCS_VOL_I16 2
+#define DCS_VOL_U16 3
+#define DCS_VOL_MAX_RADIUS 16
+#define DCS_VOL_MAX_MEDIAN 9
+#define DCS_VOL_MINMAX_PARTS 1024
+
+/* scipy.ndimage.gaussian_filter1d(mode='reflect') along axis 0 (z), 1 (y) or 2 (x).
+ * weights: HOST array of radius+1 doubles, the first half of the normalised kernel including
+ * its centre (weights[radius]); radius <= DCS_VOL_MAX_RADIUS.  (in_dtype, out_dtype) is
+ * (F32,F32), (F32,F64) [= filtering in.astype(float64)] or (F64,F64).  in != out. */
+int dcs_vol_gauss1d(const void* in, int in_dtype, void* out, int out_dtype, int D, int H, int W, int axis,
+                    int radius, const double* weights, void* stream);
+/* scipy.ndimage.median_filter(size=(k,1,1), mode='reflect') on float32; k odd, <= DCS_VOL_MAX_MEDIAN */
+int dcs_vol_median_z(const float* in, float* out, int D, int H, int W, int k, void* stream);
+/* scalar Kalman filter along z of every pixel: x = x + gain[k]*(in[k] - x), x0 = in[0], in double.
+ * gain: DEVICE array [D] (the gain sequence depends only on the two variances). */
+int dcs_vol_kalman_z(const float* in, const double* gain, double* out, int D, int H, int W, void* stream);
+/* out[0] = min, out[1] = max of n finite floats.  ws: 2*DCS_VOL_MINMAX_PARTS floats. */
+int dcs_vol_minmax(const float* x, int64_t n, float* out, float* ws, void* stream);
+/* unsharp_mask + threshold restore + int16 cast over n voxels:
+ *   detail = one_minus_amount*(sm - blur_sm) + amount*(og - blur_og), og = (double)original
+ *   v = clip(sm + detail*amount, minmax[0], minmax[1]);  original >= hu_threshold keeps original;
+ *   out = int16 truncated toward zero.  sm_dtype: DCS_VOL_F32 or DCS_VOL_F64.
+ * minmax: device float[2] of dcs_vol_minmax over the whole original volume. */
+int dcs_vol_unsharp_finish(const void* sm, int sm_dtype, const double* blur_sm, const double* blur_og,
+                           const float* original, const float* minmax, int64_t n, double one_minus_amount,
+                           double amount, float hu_threshold, int16_t* out, void* stream);
+/* the same without sharpening: threshold restore + int16 cast */
+int dcs_vol_finish(const void* sm, int sm_dtype, const float* original, int64_t n, float hu_threshold,
+                   int16_t* out, void* stream);
+/* HU-range merge of three stored-value series (generate.py:212-236): hu = f32(raw)*slope[z] +
+ * intercept[z]; voxels with soft_lo <= hu <= soft_hi take soft, then lung_lo <= hu <= lung_hi
+ * take lung.  stored_dtype: DCS_VOL_I16 or DCS_VOL_U16.  out (stored dtype) and out_f32 (the
+ * merged values as float32) are optional, at least one is required. */
+int dcs_vol_merge(const void* raw, const void* soft, const void* lung, int stored_dtype, const float* slope,
+                  const float* intercept, int D, int H, int W, float soft_lo, float soft_hi, float lung_lo,
+                  float lung_hi, void* out, float* out_f32, void* stream);
+
 /* small utilities */
 int dcs_scale_add(float* y, const float* x, float a, int64_t n, void* stream); /* y += a*x */
 /* out = x * (*s) with s a device scalar (loss backward without a host sync) */
