@@ -1,0 +1,256 @@
+"""Evaluation entry point: a drop-in for the reference's calculate.py.
+
+    python ducosy-gan_amd/calculate.py --input_dir_root ... --output_dir_root ... \
+        --dataset_names NAME [--device cuda]
+
+It converts the VUE, STD and generated DICOM series of every patient to ``.npy`` stacks sorted by
+ImagePositionPatient[2], computes MAE, PSNR, SSIM (raw and normalised) for the three pairs and
+EMD, texture similarity, cosine similarity and Euclidean distance for STD against Generated,
+and writes the reference's files under ``<output_dir_root>/calculated``:
+``data/{dataset}_{patient}_{category}.npy``, ``detail/{dataset}_{patient}_metrics.csv``,
+``result_all_metrics.pkl`` and ``summary_statistics.csv``.
+
+Differences from the reference, all deliberate:
+  * --device cuda computes the metrics on the MI355X (modules/metrics_gpu.py, csrc/metrics.hip);
+    the default, cpu, runs the numpy / scipy path of modules/metrics.py.  Both follow the
+    arithmetic fixed in modules/metrics.py;
+  * patients run one after another in this process (no process pool: --num_workers is accepted
+    and ignored);
+  * MS-SSIM and LPIPS need torchmetrics and lpips and are left empty, as the reference leaves
+    them without those libraries; the box and scatter plots need seaborn and are skipped;
+  * nothing happens at import or while parsing arguments: no environment variable is set and no
+    directory is created before the conversion starts.
+DICOM files are read with modules/dicom.py.
+"""
+import argparse
+import csv
+import glob
+import os
+import pickle
+import shutil
+import sys
+import traceback
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+
+from modules import dicom  # noqa: E402
+from modules import metrics as M  # noqa: E402
+
+CATEGORIES = ("vue", "std", "generated")
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser(description="Metrics of generated contrast-enhanced CT series")
+    p.add_argument("--data_dir_root", type=str, default="./data", help="Root directory of the data")
+    p.add_argument("--input_dir_root", type=str, default="./data/input", help="Root directory of the input datasets")
+    p.add_argument("--working_dir_root", type=str, default="./data/working", help="Root directory of inference results")
+    p.add_argument("--output_dir_root", type=str, default="./data/output",
+                   help="Root directory of the merged results and of the metrics")
+    p.add_argument("--dataset_names", type=str, nargs="+", default=["Kyunghee_Univ"], help="Dataset folder names")
+    p.add_argument("--ncct_folder", type=str, default="POST VUE", help="Folder name of the non-contrast CT")
+    p.add_argument("--cect_folder", type=str, default="POST STD", help="Folder name of the contrast-enhanced CT")
+    p.add_argument("--apply_masking", action="store_true", help="Accepted for compatibility")
+    p.add_argument("--img_size", type=int, default=512, help="Accepted for compatibility")
+    p.add_argument("--batch_size", type=int, default=4, help="Accepted for compatibility")
+    p.add_argument("--nmodel_path", type=str, default="./checkpoints/Normal_Map_Unet.pth",
+                   help="Accepted for compatibility")
+    p.add_argument("--gpu_id", type=int, default=0, help="GPU used by --device cuda")
+    p.add_argument("--fast", action="store_true", help="Accepted for compatibility")
+    p.add_argument("--reset", action="store_true", help="Remove the calculation output directory first")
+    p.add_argument("--mask", action="store_true", help="Calculate the metrics on the masked series")
+    p.add_argument("--skip_convert", action="store_true", help="Reuse the .npy stacks of an earlier run")
+    p.add_argument("--use_gpu", action="store_true", help="Accepted for compatibility (LPIPS / MS-SSIM are not computed)")
+    p.add_argument("--num_workers", type=int, default=1, help="Accepted for compatibility (patients run in sequence)")
+    p.add_argument("--device", choices=["cpu", "cuda"], default="cpu",
+                   help="cuda: compute the metrics with the HIP kernels; cpu: numpy / scipy on the host")
+    return p.parse_args(argv)
+
+
+def hu_array(dcm) -> np.ndarray:
+    intercept = dcm.RescaleIntercept if "RescaleIntercept" in dcm else 0
+    slope = dcm.RescaleSlope if "RescaleSlope" in dcm else 1
+    return dcm.pixel_array.astype(np.float32) * slope + intercept
+
+
+def series_dir(args, category, patient_dir):
+    if category == "std":
+        return os.path.join(patient_dir, args.cect_folder)
+    if category == "vue":
+        return os.path.join(patient_dir, args.ncct_folder)
+    sub = os.path.join(patient_dir, "generated")
+    return sub if os.path.exists(sub) else patient_dir
+
+
+def read_series(dcm_dir):
+    """The HU slices of a folder stacked in ImagePositionPatient[2] order, or None."""
+    slices = []
+    for path in sorted(glob.glob(os.path.join(dcm_dir, "*.dcm"))):
+        try:
+            dcm = dicom.dcmread(path)
+            z = dcm.get("ImagePositionPatient", [0.0, 0.0, 0.0])[2]
+            slices.append((hu_array(dcm), z))
+        except Exception as e:
+            print(f"Error reading {path}: {e}")
+    if not slices:
+        return None
+    slices.sort(key=lambda s: s[1])
+    return np.stack([s[0] for s in slices], axis=0)
+
+
+def convert(args):
+    """DICOM series -> .npy stacks.  Returns (output_dir, data_dir, [(dataset, patient), ...])."""
+    print("Starting DICOM to NPY conversion...")
+    out_dir = os.path.join(args.output_dir_root, "calculated_mask" if args.mask else "calculated")
+    data_dir = os.path.join(out_dir, "data")
+    if args.reset and os.path.exists(out_dir):
+        shutil.rmtree(out_dir)
+        print(f"Resetting output directory: {out_dir}")
+    os.makedirs(data_dir, exist_ok=True)
+    masked = os.path.join(args.output_dir_root, "masked")
+    roots = {"vue": masked if args.mask else args.input_dir_root,
+             "std": masked if args.mask else args.input_dir_root,
+             "generated": masked if args.mask else args.output_dir_root}
+    tasks = []
+    for category in CATEGORIES:
+        root = roots[category]
+        if not os.path.exists(root):
+            if category == "generated":
+                print(f"Warning: Generated directory not found at {root}")
+            continue
+        print(f"\nProcessing Category: {category.upper()} in {root}")
+        for dataset in args.dataset_names:
+            base = os.path.join(root, dataset)
+            if not os.path.exists(base):
+                continue
+            for patient_dir in sorted(d for d in glob.glob(os.path.join(base, "*")) if os.path.isdir(d)):
+                patient = os.path.basename(patient_dir)
+                if (dataset, patient) not in tasks:
+                    tasks.append((dataset, patient))
+                npy = os.path.join(data_dir, f"{dataset}_{patient}_{category}.npy")
+                if args.skip_convert or os.path.exists(npy):
+                    continue
+                dcm_dir = series_dir(args, category, patient_dir)
+                if not os.path.exists(dcm_dir):
+                    continue
+                stack = read_series(dcm_dir)
+                if stack is not None:
+                    np.save(npy, stack)
+    return out_dir, data_dir, tasks
+
+
+def process_patient(dataset, patient, data_dir, detail_dir, device):
+    """Metrics of one patient and its detail CSV; None when the STD or generated stack is missing."""
+    path = lambda c: os.path.join(data_dir, f"{dataset}_{patient}_{c}.npy")
+    if not (os.path.exists(path("std")) and os.path.exists(path("generated"))):
+        return None
+    try:
+        std, gen = np.load(path("std")), np.load(path("generated"))
+        vue = np.load(path("vue")) if os.path.exists(path("vue")) else None
+        if device is None:
+            patient_metrics, csv_data = M.evaluate_patient(std, gen, vue)
+        else:
+            from modules import metrics_gpu
+            patient_metrics, csv_data = metrics_gpu.evaluate_patient(std, gen, vue, device=device)
+        try:
+            M.write_detail_csv(os.path.join(detail_dir, f"{dataset}_{patient}_metrics.csv"), csv_data, vue is not None)
+        except Exception as e:
+            print(f"Error saving CSV for {patient}: {e}")
+        return patient_metrics
+    except Exception as e:
+        print(f"Error processing {patient}: {e}")
+        traceback.print_exc()
+        return None
+
+
+def calculate(out_dir, data_dir, tasks, device):
+    print(f"\nCalculating metrics for generated images (device: {device or 'cpu'})...")
+    result_path = os.path.join(out_dir, "result_all_metrics.pkl")
+    detail_dir = os.path.join(out_dir, "detail")
+    os.makedirs(detail_dir, exist_ok=True)
+    if os.path.exists(result_path):
+        with open(result_path, "rb") as f:
+            summary = pickle.load(f)
+        # as the reference: drop patients whose VUE and STD series are the same
+        drop = {i for i, v in enumerate(summary["mae"]) if len(v) > 1 and v[1] == 0.0}
+        summary = {k: [v for i, v in enumerate(vals) if i not in drop] for k, vals in summary.items()}
+        print(f"Existing results found at {result_path}. Loaded previous calculations.")
+    else:
+        summary = {k: [] for k in M.METRICS}
+        valid = 0
+        for n, (dataset, patient) in enumerate(tasks, 1):
+            res = process_patient(dataset, patient, data_dir, detail_dir, device)
+            print(f"  [{n}/{len(tasks)}] {dataset} {patient}: {'done' if res is not None else 'skipped'}")
+            if res is None:
+                continue
+            valid += 1
+            for k in summary:
+                summary[k].append(res[k])
+        if valid == 0:
+            print("No valid results found.")
+            return
+        with open(result_path, "wb") as f:
+            pickle.dump(summary, f)
+        print(f"Calculations complete. Valid patients: {valid}. Results saved to {result_path}")
+    try:
+        print("\n[Global Average: CECT(STD) vs Generated]")
+        for name, key in (("MAE ", "mae"), ("PSNR", "psnr"), ("SSIM", "ssim")):
+            print(f"{name} : {np.mean([x[0] for x in summary[key]]):.4f}")
+    except Exception:
+        print("Could not compute averages.")
+    print("Plots skipped: the reference draws them with seaborn, which is not installed.")
+
+
+def summary_statistics(detail_dir, summary_csv_path):
+    """Mean, std, min, max, median and count of every detail-CSV column over all patients."""
+    print(f"\nComputing summary statistics from {detail_dir}...")
+    files = sorted(glob.glob(os.path.join(detail_dir, "*_metrics.csv"))) if os.path.exists(detail_dir) else []
+    if not files:
+        print("No CSV files found in detail result directory.")
+        return
+    columns = {}
+    for path in files:
+        try:
+            with open(path, "r") as f:
+                for row in csv.DictReader(f):
+                    for key, value in row.items():
+                        if key == "Slice_Idx":
+                            continue
+                        try:
+                            columns.setdefault(key, []).append(float(value))
+                        except (ValueError, TypeError):
+                            pass
+        except Exception as e:
+            print(f"Error reading {path}: {e}")
+    rows = []
+    for name, values in columns.items():
+        ok = [v for v in values if np.isfinite(v)]
+        if ok:
+            rows.append({"Metric": name, "Mean": f"{np.mean(ok):.4f}", "Std": f"{np.std(ok):.4f}",
+                         "Min": f"{np.min(ok):.4f}", "Max": f"{np.max(ok):.4f}", "Median": f"{np.median(ok):.4f}",
+                         "Count": len(ok)})
+    if not rows:
+        print("No valid data to summarize.")
+        return
+    with open(summary_csv_path, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["Metric", "Mean", "Std", "Min", "Max", "Median", "Count"])
+        w.writeheader()
+        w.writerows(rows)
+    print(f"Summary statistics saved to {summary_csv_path}")
+
+
+def main(argv=None):
+    args = get_args(argv)
+    device = f"cuda:{args.gpu_id}" if args.device == "cuda" else None
+    out_dir, data_dir, tasks = convert(args)
+    if tasks:
+        calculate(out_dir, data_dir, tasks, device)
+    else:
+        print("No tasks found. Please check input directories and arguments.")
+    summary_statistics(os.path.join(out_dir, "detail"),
+                       os.path.join(out_dir, "summary_statistics_masked.csv" if args.mask else "summary_statistics.csv"))
+
+
+if __name__ == "__main__":
+    main()

@@ -42,6 +42,7 @@ KEYWORDS: Dict[str, Tuple[int, str]] = {
     "SeriesDescription": (0x0008103E, "LO"),
     "PatientID": (0x00100020, "LO"),
     "InstanceNumber": (0x00200013, "IS"),
+    "ImagePositionPatient": (0x00200032, "DS"),
     "SliceLocation": (0x00201041, "DS"),
     "SamplesPerPixel": (0x00280002, "US"),
     "PhotometricInterpretation": (0x00280004, "CS"),

@@ -1,0 +1,251 @@
+"""Evaluation metrics of calculate.py on the host: MAE, PSNR, SSIM, EMD, texture similarity,
+cosine similarity and Euclidean distance of two float32 [D,H,W] volumes, ``img1`` the target
+and ``img2`` the prediction.  Every metric returns ``(aggregate, per_slice_list)``.
+
+The formulas and branches are the reference's.  Its numerics depend on the skimage version and
+on numpy's float32 pairwise sums, so the arithmetic is fixed here, and modules/metrics_gpu.py
+(csrc/metrics.hip) follows the same rules:
+
+  * the elementwise steps of the reference's numpy expressions stay in float32: ``img1 - img2``,
+    its square, ``normalize``, the ``(s - min) / (max - min + 1e-8)`` of EMD and ED (1e-8 as a
+    float32 constant), the difference of the normalised slices;
+  * every reduction (sum, mean, norm, dot) accumulates in float64; a norm or dot squares and
+    multiplies in float64 too, as a float64 norm or dot does;
+  * skimage's structural_similarity and sobel are restated in float64 on the float32 samples;
+  * min and max are exact.
+
+ms_ssim and lpips need torchmetrics and lpips; they return ``(nan, [])`` as the reference does
+without those libraries.
+"""
+from __future__ import annotations
+
+import csv
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+from scipy.ndimage import correlate1d, uniform_filter
+
+Result = Tuple[float, List[float]]
+BASIC = ("mae", "psnr", "ssim", "mae_norm", "psnr_norm", "ssim_norm")
+ADVANCED = ("ms_ssim", "lpips", "emd", "ts", "cs", "ed")
+METRICS = BASIC + ADVANCED
+EPS32 = np.float32(1e-8)
+SSIM_WIN = 7
+
+
+def _f32(img) -> np.ndarray:
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    if a.ndim != 3:
+        raise ValueError("a [D,H,W] volume is required")
+    return a
+
+
+def _pair(img1, img2):
+    a, b = _f32(img1), _f32(img2)
+    if a.shape != b.shape:
+        raise ValueError(f"volumes differ in shape: {a.shape} and {b.shape}")
+    return a, b
+
+
+def _slice_mean(x: np.ndarray) -> np.ndarray:
+    return np.mean(x.reshape(x.shape[0], -1), axis=1, dtype=np.float64)
+
+
+def normalize(data) -> np.ndarray:
+    """Volume-global min/max to [0,1] in float32; zeros when the range is 0."""
+    data = np.asarray(data, dtype=np.float32)
+    mn, mx = data.min(), data.max()
+    if mx - mn == 0:
+        return np.zeros_like(data)
+    return (data - mn) / (mx - mn)
+
+
+def mae(img1, img2) -> Result:
+    a, b = _pair(img1, img2)
+    diff = np.abs(a - b)
+    return float(np.mean(diff, dtype=np.float64)), _slice_mean(diff).tolist()
+
+
+def psnr_from_mse(mse: float, slice_mse: Sequence[float], max_pixel: float) -> Result:
+    """PSNR's branches given the float64 mean squared errors (shared with the device path)."""
+    if mse == 0:
+        return float("inf"), [float("inf")] * len(slice_mse)
+    with np.errstate(divide="ignore"):
+        val = lambda m: float("inf") if m == 0 else float(20 * np.log10(np.float64(max_pixel) / np.sqrt(np.float64(m))))
+        return val(mse), [val(m) for m in slice_mse]
+
+
+def max_pixel_of(mn: np.float32, mx: np.float32) -> float:
+    rng = np.float32(mx) - np.float32(mn)
+    return 1.0 if rng == 0 else float(rng)
+
+
+def psnr(img1, img2) -> Result:
+    a, b = _pair(img1, img2)
+    sq = (a - b) ** 2
+    return psnr_from_mse(float(np.mean(sq, dtype=np.float64)), _slice_mean(sq), max_pixel_of(a.min(), a.max()))
+
+
+def ssim_slice(s1: np.ndarray, s2: np.ndarray, data_range: float) -> float:
+    """skimage.metrics.structural_similarity with its defaults, in float64."""
+    if min(s1.shape) < SSIM_WIN:
+        raise ValueError("win_size exceeds image extent: both sides of a slice must be at least 7")
+    x, y = s1.astype(np.float64), s2.astype(np.float64)
+    n = SSIM_WIN * SSIM_WIN
+    cov_norm = n / (n - 1.0)
+    filt = lambda v: uniform_filter(v, size=SSIM_WIN, mode="reflect")
+    ux, uy = filt(x), filt(y)
+    uxx, uyy, uxy = filt(x * x), filt(y * y), filt(x * y)
+    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+    p = (SSIM_WIN - 1) // 2
+    return float(np.mean(s[p:s.shape[0] - p, p:s.shape[1] - p], dtype=np.float64))
+
+
+def ssim(img1, img2) -> Result:
+    a, b = _pair(img1, img2)
+    if a.shape[1] < SSIM_WIN or a.shape[2] < SSIM_WIN:
+        raise ValueError("win_size exceeds image extent: both sides of a slice must be at least 7")
+    data_range = float(b.max() - b.min())
+    vals = [ssim_slice(s1, s2, data_range) for s1, s2 in zip(a, b)]
+    return float(np.mean(vals)), vals
+
+
+def ms_ssim(img1, img2) -> Result:
+    return float("nan"), []
+
+
+def lpips(img1, img2) -> Result:
+    return float("nan"), []
+
+
+def emd(img1, img2) -> Result:
+    """Wasserstein-1 distance of the two globally normalised slices over H*W: for samples of
+    equal size it is the mean absolute difference of the sorted samples."""
+    a, b = _pair(img1, img2)
+    gmin = min(a.min(), b.min())
+    div = np.float32(max(a.max(), b.max()) - gmin) + EPS32
+    vals = []
+    for s1, s2 in zip(a, b):
+        u = np.sort(((s1 - gmin) / div).ravel())
+        v = np.sort(((s2 - gmin) / div).ravel())
+        vals.append(float(np.mean(np.abs(u - v), dtype=np.float64) / s1.size))
+    return float(np.mean(vals)), vals
+
+
+def sobel(s: np.ndarray) -> np.ndarray:
+    """skimage.filters.sobel of a 2-D image in float64."""
+    x = s.astype(np.float64)
+    smooth, edge = np.array([0.25, 0.5, 0.25]), np.array([1.0, 0.0, -1.0])
+    h = correlate1d(correlate1d(x, edge, axis=0, mode="reflect"), smooth, axis=1, mode="reflect")
+    v = correlate1d(correlate1d(x, edge, axis=1, mode="reflect"), smooth, axis=0, mode="reflect")
+    return np.sqrt((h * h + v * v) / 2)
+
+
+def ts_from_sums(sum_abs: float, max1: float, max2: float, n: int) -> float:
+    m = max(max1, max2)
+    return float(1.0 - (sum_abs / n) / m) if m > 0 else 1.0
+
+
+def ts(img1, img2) -> Result:
+    a, b = _pair(img1, img2)
+    vals = []
+    for s1, s2 in zip(a, b):
+        g1, g2 = sobel(s1), sobel(s2)
+        vals.append(ts_from_sums(float(np.sum(np.abs(g1 - g2), dtype=np.float64)), float(g1.max()), float(g2.max()),
+                                 s1.size))
+    return float(np.mean(vals)), vals
+
+
+def cs_from_sums(sab, saa, sbb) -> float:
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(np.float64(sab) / (np.sqrt(np.float64(saa)) * np.sqrt(np.float64(sbb))))
+
+
+def cs(img1, img2) -> Result:
+    a, b = _pair(img1, img2)
+    vals = []
+    for s1, s2 in zip(a, b):
+        x, y = s1.ravel().astype(np.float64), s2.ravel().astype(np.float64)
+        vals.append(cs_from_sums(np.dot(x, y), np.dot(x, x), np.dot(y, y)))
+    return float(np.mean(vals)), vals
+
+
+def ed(img1, img2) -> Result:
+    a, b = _pair(img1, img2)
+    vals = []
+    for s1, s2 in zip(a, b):
+        n1 = (s1 - s1.min()) / (s1.max() - s1.min() + EPS32)
+        n2 = (s2 - s2.min()) / (s2.max() - s2.min() + EPS32)
+        d = (n1 - n2).astype(np.float64)
+        vals.append(float(np.sqrt(np.sum(d * d, dtype=np.float64)) / s1.size))
+    return float(np.mean(vals)), vals
+
+
+def evaluate_pair(target, pred, advanced: bool = True) -> Dict[str, Result]:
+    """The basic metrics on the raw and the normalised volumes, and the advanced ones if asked."""
+    t, p = _pair(target, pred)
+    tn, pn = normalize(t), normalize(p)
+    out = {"mae": mae(t, p), "psnr": psnr(t, p), "ssim": ssim(t, p),
+           "mae_norm": mae(tn, pn), "psnr_norm": psnr(tn, pn), "ssim_norm": ssim(tn, pn)}
+    if advanced:
+        out.update({"ms_ssim": ms_ssim(tn, pn), "lpips": lpips(tn, pn), "emd": emd(t, p), "ts": ts(t, p),
+                    "cs": cs(t, p), "ed": ed(t, p)})
+    return out
+
+
+def pair_names(has_vue: bool) -> List[str]:
+    return ["STD_vs_Generated"] + (["VUE_vs_STD", "VUE_vs_Generated"] if has_vue else [])
+
+
+def collect_patient(pair_fn, std, gen, vue=None):
+    """The per-patient driver both paths share: the basic metrics for every pair, the advanced
+    ones for STD against Generated; series are cut to the shortest.  ``pair_fn(target, pred,
+    advanced)`` is evaluate_pair of the host or of the device module.  Returns (patient_metrics,
+    csv_data): per metric the list of aggregates and the list of per-slice lists, one per pair."""
+    n = min(len(v) for v in (std, gen, vue) if v is not None)
+    std, gen = std[:n], gen[:n]
+    pairs = [(std, gen, True)]
+    if vue is not None:
+        vue = vue[:n]
+        pairs += [(vue, std, False), (vue, gen, False)]
+    patient = {k: [] for k in METRICS}
+    per_slice = {k: [] for k in METRICS}
+    for targ, pred, adv in pairs:
+        for k, (agg, lst) in pair_fn(targ, pred, adv).items():
+            patient[k].append(agg)
+            per_slice[k].append(lst)
+    return patient, per_slice
+
+
+def evaluate_patient(std, gen, vue=None):
+    return collect_patient(evaluate_pair, std, gen, vue)
+
+
+def detail_header(has_vue: bool) -> List[str]:
+    names = pair_names(has_vue)
+    return (["Slice_Idx"] + [f"{m}_{p}" for m in BASIC for p in names]
+            + [f"{m}_STD_vs_Generated" for m in ADVANCED])
+
+
+def detail_rows(csv_data: Dict[str, list], has_vue: bool) -> List[list]:
+    npairs = len(pair_names(has_vue))
+    rows = []
+    for i in range(min(len(l) for l in csv_data["mae"])):
+        row = [i]
+        for m in BASIC:
+            row += [csv_data[m][j][i] if j < len(csv_data[m]) else "" for j in range(npairs)]
+        for m in ADVANCED:
+            vals = csv_data[m]
+            row.append(vals[0][i] if vals and i < len(vals[0]) else "")
+        rows.append(row)
+    return rows
+
+
+def write_detail_csv(path: str, csv_data: Dict[str, list], has_vue: bool) -> None:
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(detail_header(has_vue))
+        w.writerows(detail_rows(csv_data, has_vue))

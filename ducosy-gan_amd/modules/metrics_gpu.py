@@ -1,0 +1,175 @@
+"""Evaluation metrics of calculate.py on the device (csrc/metrics.hip through modules/hip/metrics.py).
+
+The same functions as modules/metrics.py, on float32 [D,H,W] device tensors: every metric
+returns ``(aggregate, per_slice_list)`` and follows the arithmetic fixed in that module's
+docstring, so the two paths agree to the rounding of float64 sums taken in different orders
+(tests/test_gpu_metrics.py).  A volume is read by a handful of bandwidth-bound passes:
+
+  * one pass over the pair gives the per-slice sums behind MAE, PSNR and cosine similarity and
+    the min/max of both volumes (``PairStats``);
+  * the ``*_norm`` variants read the raw volumes again and normalise on the fly, bit for bit as
+    ``normalize`` does, so no normalised copy is written;
+  * SSIM, the Sobel texture similarity and the Euclidean distance take one pass each; EMD sorts
+    the raw rows with torch.sort (plumbing) and takes one more pass.  The float32 normalisation
+    ``(x - min) / div`` with div > 0 is monotone, so sorting before it gives the same sorted
+    normalised samples as sorting after it.
+
+Only per-slice float64 vectors come back to the host.  No CPU fallback: host tensors raise.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import metrics as M
+from .hip import metrics as K
+
+Result = M.Result
+
+
+def _rng32(mn, mx) -> np.float32:
+    return np.float32(mx) - np.float32(mn)
+
+
+class PairStats:
+    """The per-slice sums and extrema of a (target, prediction) pair, on the host."""
+
+    def __init__(self, a: torch.Tensor, b: torch.Tensor, affine=None):
+        self.dev = K.pair_stats(a, b, affine)
+        self.h = self.dev.cpu().numpy()
+        self.D, self.n = a.shape[0], a.shape[1] * a.shape[2]
+        h = self.h
+        self.amin, self.amax = np.float32(h[:, K.MIN_A].min()), np.float32(h[:, K.MAX_A].max())
+        self.bmin, self.bmax = np.float32(h[:, K.MIN_B].min()), np.float32(h[:, K.MAX_B].max())
+
+    def mae(self) -> Result:
+        s = self.h[:, K.SUM_ABS]
+        return float(s.sum() / (self.D * self.n)), (s / self.n).tolist()
+
+    def psnr(self) -> Result:
+        s = self.h[:, K.SUM_SQ]
+        return M.psnr_from_mse(float(s.sum() / (self.D * self.n)), s / self.n, M.max_pixel_of(self.amin, self.amax))
+
+    def cs(self) -> Result:
+        vals = [M.cs_from_sums(r[K.SUM_AB], r[K.SUM_AA], r[K.SUM_BB]) for r in self.h]
+        return float(np.mean(vals)), vals
+
+    def normalize_affine(self):
+        """(a_off, a_div, b_off, b_div) of normalize() on each volume; div 0 stands for zeros."""
+        return (float(self.amin), float(_rng32(self.amin, self.amax)),
+                float(self.bmin), float(_rng32(self.bmin, self.bmax)))
+
+
+def _check_window(a) -> None:
+    """SSIM's shape error, raised before anything is launched."""
+    if isinstance(a, torch.Tensor) and a.dim() == 3 and min(a.shape[1:]) < M.SSIM_WIN:
+        raise ValueError("ssim: win_size exceeds image extent: both sides of a slice must be at least 7")
+
+
+def _ssim(a, b, data_range: float, affine=None) -> Result:
+    sums = K.ssim_sums(a, b, data_range, affine).cpu().numpy()
+    vals = (sums / ((a.shape[1] - 6) * (a.shape[2] - 6))).tolist()
+    return float(np.mean(vals)), vals
+
+
+def _emd(a, b, st: PairStats) -> Result:
+    gmin = min(st.amin, st.bmin)
+    div = np.float32(max(st.amax, st.bmax) - gmin) + M.EPS32
+    D = a.shape[0]
+    # sorting the raw rows: the normalisation is monotone, see the module docstring
+    sa = torch.sort(a.reshape(D, -1), dim=1).values.reshape(a.shape)
+    sb = torch.sort(b.reshape(D, -1), dim=1).values.reshape(b.shape)
+    sums = K.sorted_l1(sa, sb, (float(gmin), float(div), float(gmin), float(div))).cpu().numpy()
+    vals = (sums / st.n / st.n).tolist()
+    return float(np.mean(vals)), vals
+
+
+def _ts(a, b) -> Result:
+    r = K.sobel_ts(a, b).cpu().numpy()
+    n = a.shape[1] * a.shape[2]
+    vals = [M.ts_from_sums(float(s), float(m1), float(m2), n) for s, m1, m2 in r]
+    return float(np.mean(vals)), vals
+
+
+def _ed(a, b, st: PairStats) -> Result:
+    sums = K.ed_sums(a, b, st.dev).cpu().numpy()
+    vals = (np.sqrt(sums) / st.n).tolist()
+    return float(np.mean(vals)), vals
+
+
+def minmax(x: torch.Tensor):
+    """(min, max) of a device volume as numpy float32, exact."""
+    st = PairStats(x, x)
+    return st.amin, st.amax
+
+
+def normalize(x: torch.Tensor) -> torch.Tensor:
+    mn, mx = minmax(x)
+    return K.normalize(x, float(mn), float(_rng32(mn, mx)))
+
+
+def mae(img1, img2) -> Result:
+    return PairStats(img1, img2).mae()
+
+
+def psnr(img1, img2) -> Result:
+    return PairStats(img1, img2).psnr()
+
+
+def cs(img1, img2) -> Result:
+    return PairStats(img1, img2).cs()
+
+
+def ssim(img1, img2) -> Result:
+    _check_window(img1)
+    st = PairStats(img1, img2)
+    return _ssim(img1, img2, float(_rng32(st.bmin, st.bmax)))
+
+
+def emd(img1, img2) -> Result:
+    return _emd(img1, img2, PairStats(img1, img2))
+
+
+def ts(img1, img2) -> Result:
+    return _ts(img1, img2)
+
+
+def ed(img1, img2) -> Result:
+    return _ed(img1, img2, PairStats(img1, img2))
+
+
+ms_ssim, lpips = M.ms_ssim, M.lpips
+
+
+def to_device(x, device) -> torch.Tensor:
+    """A float32 device tensor of a numpy array or tensor (one upload)."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    return x.to(device=device, dtype=torch.float32)
+
+
+def evaluate_pair(target, pred, device, advanced: bool = True) -> Dict[str, Result]:
+    """modules/metrics.py::evaluate_pair on ``device``."""
+    t, p = to_device(target, device), to_device(pred, device)
+    _check_window(t)
+    st = PairStats(t, p)
+    aff = st.normalize_affine()
+    stn = PairStats(t, p, aff)
+    out = {"mae": st.mae(), "psnr": st.psnr(), "ssim": _ssim(t, p, float(_rng32(st.bmin, st.bmax))),
+           "mae_norm": stn.mae(), "psnr_norm": stn.psnr(),
+           "ssim_norm": _ssim(t, p, float(_rng32(stn.bmin, stn.bmax)), aff)}
+    if advanced:
+        out.update({"ms_ssim": ms_ssim(None, None), "lpips": lpips(None, None), "emd": _emd(t, p, st),
+                    "ts": _ts(t, p), "cs": st.cs(), "ed": _ed(t, p, st)})
+    return out
+
+
+def evaluate_patient(std, gen, vue=None, device: Optional[object] = "cuda"):
+    """modules/metrics.py::evaluate_patient; ``device=None`` runs the host module, anything else
+    uploads every series once and keeps the work on that device."""
+    if device is None:
+        return M.evaluate_patient(std, gen, vue)
+    up = lambda v: None if v is None else to_device(v, device)
+    return M.collect_patient(lambda t, p, adv: evaluate_pair(t, p, device, adv), up(std), up(gen), up(vue))

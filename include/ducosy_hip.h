@@ -643,6 +643,47 @@ int dcs_vol_merge(const void* raw, const void* soft, const void* lung, int store
                   const float* intercept, int D, int H, int W, float soft_lo, float soft_hi, float lung_lo,
                   float lung_hi, void* out, float* out_f32, void* stream);
 
+/* ---- evaluation metrics (calculate.py's MAE, PSNR, SSIM, EMD, texture similarity, cosine
+ *      similarity and Euclidean distance; modules/metrics.py on the host) ----
+ * a (target) and b (prediction): dense float32 [D][H][W] device volumes, x fastest.  Every result
+ * is float64 per slice.  Arithmetic: the float32 elementwise steps of the numpy expressions
+ * (a - b, its square, (x - off) / div), float64 accumulation of every sum, SSIM and Sobel in
+ * float64.  No floating-point atomics: per-workgroup float64 partials go to the caller's
+ * workspace ws (dcs_met_workspace_size bytes serve every entry point) and are folded in a fixed
+ * order, so results are bit-identical from run to run.  Every entry point checks its arguments on
+ * the host before any launch and returns DCS_E_INVALID (DCS_E_WORKSPACE for a short workspace).
+ * affine: optional HOST array {a_off, a_div, b_off, b_div}; the kernels then read
+ * (x - off) / div in float32 (0 where div == 0) in place of x, which is calculate.py's
+ * normalize() for off = min, div = max - min.  NULL reads the volumes as they are. */
+#define DCS_MET_NSTATS 9
+#define DCS_MET_TILE_X 64 /* output tile of dcs_met_ssim and dcs_met_sobel_ts */
+#define DCS_MET_TILE_Y 32
+#define DCS_MET_PAIR_CHUNK 8192 /* voxels of one slice per workgroup of the pair passes */
+/* bytes of workspace for a [D][H][W] pair; 0 for dimensions the entry points refuse */
+size_t dcs_met_workspace_size(int D, int H, int W);
+/* one pass over both volumes: out[z][0..8] = sum|a-b|, sum f32((a-b)^2), sum ab, sum a^2,
+ * sum b^2, min a, max a, min b, max b of slice z (MAE, PSNR, cosine similarity, global range) */
+int dcs_met_pair_stats(const float* a, const float* b, int D, int H, int W, const float* affine, double* out,
+                       void* ws, size_t ws_bytes, void* stream);
+/* out[z] = the SUM of skimage's structural_similarity map (7x7 uniform window, sample covariance,
+ * K1 0.01, K2 0.03) over the interior cropped by 3; the mean divides by (H-6)(W-6).  H, W >= 7. */
+int dcs_met_ssim(const float* a, const float* b, int D, int H, int W, const float* affine, double data_range,
+                 double* out, void* ws, size_t ws_bytes, void* stream);
+/* skimage.filters.sobel (mode reflect) of both slices on the fly:
+ * out[z][0..2] = sum|g1 - g2|, max g1, max g2 */
+int dcs_met_sobel_ts(const float* a, const float* b, int D, int H, int W, double* out, void* ws, size_t ws_bytes,
+                     void* stream);
+/* out[z] = sum (a_n - b_n)^2, each slice normalised in float32 by its own (x - min) / (max - min + 1e-8f);
+ * stats: the device result of dcs_met_pair_stats on the same pair without affine */
+int dcs_met_ed(const float* a, const float* b, int D, int H, int W, const double* stats, double* out, void* ws,
+               size_t ws_bytes, void* stream);
+/* out[z] = sum|a_n - b_n| of two volumes whose slices are sorted (EMD: the Wasserstein-1 distance
+ * of equal-sized samples is the mean of this) */
+int dcs_met_sorted_l1(const float* a, const float* b, int D, int H, int W, const float* affine, double* out,
+                      void* ws, size_t ws_bytes, void* stream);
+/* out = (x - off) / div in float32, 0 where div == 0 (calculate.py's normalize) */
+int dcs_met_normalize(const float* x, int64_t n, float off, float div, float* out, void* stream);
+
 /* small utilities */
 int dcs_scale_add(float* y, const float* x, float a, int64_t n, void* stream); /* y += a*x */
 /* out = x * (*s) with s a device scalar (loss backward without a host sync) */

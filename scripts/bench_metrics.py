@@ -1,0 +1,173 @@
+#!/usr/bin/env python
+"""Host against device timing of calculate.py's per-patient metrics (modules/metrics_gpu.py::evaluate_patient).
+
+    python scripts/bench_metrics.py [--shape 128x512x512] [--reps 5] [--host_reps 5] [--skip_host]
+
+One synthetic patient from modules/phantom.py (STD, a generated series = STD + rounded N(0, 20),
+a VUE series) goes through
+  * the host path (``device=None``: numpy / scipy of modules/metrics.py, this process's threads),
+    median of --host_reps after one warm-up;
+  * the device path end to end: upload of the three float32 series, kernels, download of the
+    per-slice vectors, median of --reps after one warm-up;
+  * every kernel alone on resident volumes, from HIP events, median of --reps after one warm-up,
+    with its algorithmic bytes (both volumes read once, 8 bytes per voxel) over that time as a
+    share of the 8 TB/s HBM peak.
+The two paths' results are compared at the bars of tests/test_gpu_metrics.py.  Prints progress
+lines and, last, one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path.insert(0, os.path.join(ROOT, "ducosy-gan_amd"))
+
+from modules import metrics as M  # noqa: E402
+from modules import metrics_gpu as G  # noqa: E402
+from modules import phantom  # noqa: E402
+from modules.hip import metrics as K  # noqa: E402
+
+HBM_PEAK = 8.0e12
+
+
+def patient(shape, seed=0):
+    d, h, w = shape
+    assert h == w, "the phantom draws square slices"
+    raw, slope, inter = phantom.ct_batch(seed, d, h, kinds=["chest"])
+    std = raw.astype(np.float32) * slope[:, None, None] + inter[:, None, None]
+    rng = np.random.default_rng(seed + 1)
+    gen = (std + np.round(rng.normal(0, 20, std.shape))).astype(np.float32)
+    vue = (std - np.where((std > 200) & (std < 400), 250, 0) + np.round(rng.normal(0, 10, std.shape))).astype(np.float32)
+    return std, gen, vue
+
+
+def _events(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def _median_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    return statistics.median(_events(fn) for _ in range(reps))
+
+
+def kernel_times(std, gen, reps):
+    """Event time of every kernel on one resident pair, with its share of the HBM peak."""
+    t, p = std, gen
+    st = K.pair_stats(t, p)
+    aff = G.PairStats(t, p).normalize_affine()
+    D = t.shape[0]
+    sa = torch.sort(t.reshape(D, -1), dim=1).values.reshape(t.shape)
+    sb = torch.sort(p.reshape(D, -1), dim=1).values.reshape(p.shape)
+    runs = {
+        "pair_stats": lambda: K.pair_stats(t, p),
+        "pair_stats_norm": lambda: K.pair_stats(t, p, aff),
+        "ssim": lambda: K.ssim_sums(t, p, 2500.0),
+        "ssim_norm": lambda: K.ssim_sums(t, p, 1.0, aff),
+        "sobel_ts": lambda: K.sobel_ts(t, p),
+        "ed": lambda: K.ed_sums(t, p, st),
+        "sorted_l1": lambda: K.sorted_l1(sa, sb, (-1024.0, 4000.0, -1024.0, 4000.0)),
+        "torch_sort_x2": lambda: (torch.sort(t.reshape(D, -1), dim=1), torch.sort(p.reshape(D, -1), dim=1)),
+    }
+    nbytes = 8 * t.numel()
+    out = {}
+    for name, fn in runs.items():
+        ms = _median_ms(fn, reps)
+        out[name] = {"ms": round(ms, 4)}
+        if name != "torch_sort_x2":
+            out[name]["algorithmic_GBps"] = round(nbytes / ms / 1e6, 1)
+            out[name]["share_of_hbm_peak"] = round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)
+    return out
+
+
+def _agree(got, want):
+    worst = {"rel": 0.0, "ssim_abs": 0.0}
+    ok = True
+    for k in M.METRICS:
+        for gl, wl in zip(got[1][k], want[1][k]):
+            g, w = np.array(gl, np.float64), np.array(wl, np.float64)
+            ok &= g.shape == w.shape and np.array_equal(np.isfinite(g), np.isfinite(w))
+            f = np.isfinite(w)
+            if not f.any():
+                continue
+            err = np.abs(g[f] - w[f])
+            if k.startswith("ssim"):
+                worst["ssim_abs"] = max(worst["ssim_abs"], float(err.max()))
+            else:
+                worst["rel"] = max(worst["rel"], float((err / np.maximum(np.abs(w[f]), 1e-300)).max()))
+    return bool(ok and worst["rel"] <= 1e-10 and worst["ssim_abs"] <= 1e-10), worst
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", default="128x512x512")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host_reps", type=int, default=5)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--skip_host", action="store_true", help="device times only (no comparison)")
+    a = ap.parse_args()
+    dev = torch.device(a.device)
+    shape = tuple(int(x) for x in a.shape.split("x"))
+    threads = min(16, len(os.sched_getaffinity(0)))
+    torch.set_num_threads(threads)
+    t0 = time.perf_counter()
+    std, gen, vue = patient(shape)
+    print(f"phantom patient {shape} in {time.perf_counter() - t0:.1f} s", flush=True)
+    res = {"metric": "evaluate_patient_seconds", "device": torch.cuda.get_device_name(dev), "shape": a.shape,
+           "host_threads": threads}
+
+    def device_run():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = G.evaluate_patient(std, gen, vue, device=dev)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    device_run()
+    times = []
+    for i in range(a.reps):
+        dt, got = device_run()
+        times.append(dt)
+        print(f"device run {i}: {dt:.4f} s", flush=True)
+    res["device_end_to_end_s"] = round(statistics.median(times), 4)
+
+    ds, dg, dv = (G.to_device(v, dev) for v in (std, gen, vue))
+    resident = lambda: G.evaluate_patient(ds, dg, dv, device=dev)
+    resident()
+    torch.cuda.synchronize()
+    res["device_resident_ms"] = round(statistics.median(_events(resident) for _ in range(a.reps)), 3)
+    res["kernels"] = kernel_times(ds, dg, a.reps)
+    del ds, dg, dv
+    print("device:", json.dumps({k: res[k] for k in ("device_end_to_end_s", "device_resident_ms")}), flush=True)
+
+    if not a.skip_host:
+        times = []
+        for i in range(a.host_reps + 1):
+            t0 = time.perf_counter()
+            want = G.evaluate_patient(std, gen, vue, device=None)
+            dt = time.perf_counter() - t0
+            print(f"host run {i}{' (warm-up)' if i == 0 else ''}: {dt:.2f} s", flush=True)
+            if i:
+                times.append(dt)
+        res["host_s"] = round(statistics.median(times), 3)
+        res["agree"], res["worst_error"] = _agree(got, want)
+        res["speedup_end_to_end"] = round(res["host_s"] / res["device_end_to_end_s"], 1)
+        res["speedup_resident"] = round(res["host_s"] * 1e3 / res["device_resident_ms"], 1)
+    print(json.dumps(res))
+    if not a.skip_host and not res["agree"]:
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()
