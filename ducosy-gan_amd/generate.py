@@ -14,7 +14,11 @@ Differences from the reference, all deliberate:
   * checkpoints are read with torch.load(weights_only=True);
   * --postprocess_device cuda runs the synthesis stage's HU-range merge and volume smoothing on
     the GPU (modules/postprocess_gpu.py, csrc/volume.hip) instead of scipy on the host: one
-    upload of the three series, one download of the int16 volume, identical output files.
+    upload of the three series, one download of the int16 volume, identical output files;
+  * --pipeline resident (generate_synthesis) runs both stages in one pass per patient: stored
+    NCCT pixels go up once, HU transform, masks, resizes, both Generators, the output -> stored
+    value map, the merge and the smoothing stay on the GPU (csrc/slices.hip, csrc/volume.hip), the
+    int16 volume comes down once; no working series is written unless --write_working is given.
 DICOM reading/writing uses modules/dicom.py (pydicom is not installed in this image).
 """
 import argparse
@@ -30,8 +34,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from modules.inference import (hu_from_stored, normalise_hu, smooth_volume, stored_from_output,  # noqa: E402
-                               synthesize, synthesize_volume, translate_slices)
+from modules.inference import (MASK_TYPES, _conditioning, hu_from_stored, normalise_hu,  # noqa: E402,F401
+                               smooth_volume, smooth_volume_device, stored_from_output, synthesize,
+                               synthesize_volume, translate_slices, translate_volume_device)
 from modules.model import Generator  # noqa: E402
 
 
@@ -44,26 +49,6 @@ def load_generator(path, device, num_residual_blocks=9):
     g = Generator(input_channels=cin, num_residual_blocks=num_residual_blocks)
     g.load_state_dict(sd)
     return g.to(device).eval()
-
-
-MASK_TYPES = {"soft_tissue": ["bone", "mediastinum"], "lung": ["lung"]}  # argmanager.py:132, 149
-
-
-def _conditioning(g, kind, hu_slices, device):
-    """Per-slice mask channels for a mask-conditioned Generator (None for an image-only one):
-    the training mask types when their count matches the checkpoint, else zero planes."""
-    extra = g.input_channels - 1
-    if extra <= 0:
-        return None
-    types = MASK_TYPES[kind]
-    if len(types) != extra:
-        return [np.zeros((extra,) + h.shape, np.float32) for h in hu_slices]
-    from modules.hip import ops
-    out = []
-    for h in hu_slices:
-        m = ops.anatomical_masks(torch.from_numpy(np.ascontiguousarray(h, np.float32)).to(device), types)
-        out.append(m[0].cpu().numpy())
-    return out
 
 
 def _model_args(args, soft_tissue_args, lung_args):
@@ -175,6 +160,87 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
     print("\nSynthesis complete.")
 
 
+def _write_translation(d, px, path):
+    """One slice of a working series, as generate() writes it."""
+    from modules import dicom
+    o = deepcopy(d)
+    o.SeriesDescription = f"Synthetic CECT (from {d.get('SeriesDescription', '')})"
+    o.file_meta.TransferSyntaxUID = dicom.EXPLICIT_VR_LE
+    o.SmallestImagePixelValue, o.LargestImagePixelValue = int(px.min()), int(px.max())
+    o.PixelData = px.tobytes()
+    o.save_as(path)
+
+
+def generate_synthesis(args, soft_tissue_args=None, lung_args=None):
+    """--pipeline resident: generate() and synthesis() in one pass per patient, with everything
+    between the upload of the NCCT stored values and the download of the smoothed int16 volume
+    resident on the GPU (modules/inference.py::translate_volume_device, smooth_volume_device).
+    Writes output/{dataset}/{patient}/{idx:04d}.dcm with the pixels and header edits the staged
+    path ends up with, and no working series unless --write_working asks for them.
+
+    Slices of one patient that differ in size or stored dtype are processed as one volume per
+    (size, dtype) group, each smoothed along z on its own, and written under their series index."""
+    from modules import dicom
+    sa, la = _model_args(args, soft_tissue_args, lung_args)
+    device = torch.device(f"cuda:{args.gpu_id}")
+    soft = load_generator(sa.model_path, device)
+    lung = load_generator(la.model_path, device)
+    batch = int(getattr(args, "slice_batch", 16))
+    write_working = bool(getattr(args, "write_working", False))
+    soft_range, lung_range = (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max)
+    for dataset_name in args.dataset_names:
+        input_dir = os.path.join(args.input_dir_root, dataset_name)
+        working_dir = os.path.join(args.working_dir_root, dataset_name)
+        output_dir = os.path.join(args.output_dir_root, dataset_name)
+        for patient_dir in sorted(d for d in glob.glob(os.path.join(input_dir, "*")) if os.path.isdir(d)):
+            ncct = os.path.join(patient_dir, args.ncct_folder)
+            if not os.path.isdir(ncct):
+                continue
+            patient = os.path.basename(patient_dir)
+            paths = sorted(glob.glob(os.path.join(ncct, "*.dcm")))
+            if not paths:
+                continue
+            dcms = [dicom.dcmread(p) for p in paths]
+            pixels = [d.pixel_array for d in dcms]
+            groups = {}
+            for i, px in enumerate(pixels):
+                groups.setdefault((px.shape, px.dtype.str), []).append(i)
+            if len(groups) > 1:
+                print(f"{patient}: {len(groups)} slice formats; each is translated and smoothed as its own volume")
+            out_base = os.path.join(output_dir, patient)
+            os.makedirs(out_base, exist_ok=True)
+            work = {k: os.path.join(working_dir, patient, k) for k in ("raw", "soft_tissue", "lung")}
+            if write_working:
+                for d in work.values():
+                    os.makedirs(d, exist_ok=True)
+            for idxs in groups.values():
+                raw = np.stack([pixels[i] for i in idxs])
+                res = translate_volume_device(
+                    soft, lung, raw, [getattr(dcms[i], "RescaleSlope", 1) for i in idxs],
+                    [getattr(dcms[i], "RescaleIntercept", 0) for i in idxs], soft_range, lung_range,
+                    args.img_size, batch, device, want_stored=write_working)
+                merged = res[0] if write_working else res
+                vol = smooth_volume_device(merged).cpu().numpy()
+                if write_working:
+                    series = {k: t.cpu().numpy().view(raw.dtype) for k, t in (("soft_tissue", res[1]), ("lung", res[2]))}
+                for k, i in enumerate(idxs):
+                    d, name = dcms[i], os.path.basename(paths[i])
+                    if write_working:
+                        shutil.copy(paths[i], os.path.join(work["raw"], name))
+                        for kind, s in series.items():
+                            _write_translation(d, s[k], os.path.join(work[kind], name))
+                    o, px = deepcopy(d), vol[k]
+                    o.file_meta.TransferSyntaxUID = dicom.EXPLICIT_VR_LE
+                    o.PixelData = px.tobytes()
+                    vr = "US" if o.PixelRepresentation == 0 else "SS"
+                    o.add_new((0x0028, 0x0106), vr, int(px.min()))
+                    o.add_new((0x0028, 0x0107), vr, int(px.max()))
+                    o.WindowWidth, o.WindowCenter = 1250, -375.0   # generate.py:279-282
+                    o.SeriesDescription = "DuCoSyGAN sCECT v2"
+                    o.save_as(os.path.join(out_base, f"{i:04d}.dcm"))
+    print("\nGeneration and synthesis complete.")
+
+
 def get_args(argv=None):
     """The reference's inference arguments (modules/argmanager.py:4-81) in one parser (the
     reference parses sys.argv three times with three parsers, generate.py:483-485)."""
@@ -196,12 +262,24 @@ def get_args(argv=None):
     p.add_argument("--skip_convert", action="store_true", help="only run the synthesis stage")
     p.add_argument("--postprocess_device", choices=["cpu", "cuda"], default="cpu",
                    help="where the synthesis stage merges and smooths the volume (cuda: cuda:{gpu_id})")
+    p.add_argument("--pipeline", choices=["staged", "resident"], default="staged",
+                   help="staged: generate() then synthesis() through the working directory; resident: one pass "
+                        "per patient on the GPU (generate_synthesis), no working series unless --write_working; "
+                        "with --skip_convert the staged synthesis() runs on the working series either way")
+    p.add_argument("--write_working", action="store_true",
+                   help="--pipeline resident: also write the raw / soft_tissue / lung working series")
     return p.parse_args(argv)
 
 
 if __name__ == "__main__":
     a = get_args()
     soft_a, lung_a = _model_args(a, None, None)
-    if not a.skip_convert:
-        generate(a, soft_a, lung_a)
-    synthesis(a, soft_a, lung_a)
+    if a.pipeline == "resident" and not a.skip_convert:
+        generate_synthesis(a, soft_a, lung_a)
+    else:
+        if a.pipeline == "resident":
+            print("--skip_convert: running the staged synthesis() on the working series (--pipeline resident "
+                  "has no stage of its own to skip to)")
+        if not a.skip_convert:
+            generate(a, soft_a, lung_a)
+        synthesis(a, soft_a, lung_a)

@@ -19,6 +19,7 @@ RANGE_PARTS = 512  # DCS_RANGE_PARTS: partial maxima of an f16x3 operand's range
 KORDER_TAP, KORDER_SLICE, PACK_KSLICE = 0, 1, 8
 VOL_F32, VOL_F64, VOL_I16, VOL_U16 = 0, 1, 2, 3  # DCS_VOL_* dtypes
 VOL_MAX_RADIUS, VOL_MAX_MEDIAN, VOL_MINMAX_PARTS = 16, 9, 1024
+RESIZE_MAX_TAPS = 18  # DCS_RESIZE_MAX_TAPS
 MET_NSTATS, MET_TILE_X, MET_TILE_Y, MET_PAIR_CHUNK = 9, 64, 32, 8192  # DCS_MET_*
 
 
@@ -179,6 +180,10 @@ SIGNATURES = {
     "dcs_vol_finish": (c_int, [P, c_int, P, c_int64, c_float, P, P]),
     "dcs_vol_merge": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
                               P, P, P]),
+    "dcs_vol_translate_merge": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                        c_float, c_float, P, P, P, P, P]),
+    "dcs_resize_aa": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P]),
+    "dcs_resize_nearest": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "dcs_met_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "dcs_met_pair_stats": (c_int, [P, P, c_int, c_int, c_int, POINTER(c_float), P, P, c_size_t, P]),
     "dcs_met_ssim": (c_int, [P, P, c_int, c_int, c_int, POINTER(c_float), c_double, P, P, c_size_t, P]),

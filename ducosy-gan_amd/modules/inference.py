@@ -66,6 +66,100 @@ def translate_slices(model, slices: Sequence[np.ndarray], img_size: int, batch: 
     return out
 
 
+MASK_TYPES = {"soft_tissue": ["bone", "mediastinum"], "lung": ["lung"]}  # argmanager.py:132, 149
+
+
+def conditioning_types(g, kind: str, mask_types=MASK_TYPES) -> Tuple[int, Optional[List[str]]]:
+    """The conditioning rule of a Generator at inference: (mask channel count, mask types).
+    0 channels for an image-only Generator; the training mask types of ``kind`` when their count
+    matches the checkpoint's extra input channels, else None: zero planes."""
+    extra = g.input_channels - 1
+    if extra <= 0:
+        return 0, None
+    types = list(mask_types[kind])
+    return extra, (types if len(types) == extra else None)
+
+
+def _conditioning(g, kind, hu_slices, device, mask_types=MASK_TYPES):
+    """Per-slice mask channels for a mask-conditioned Generator (None for an image-only one):
+    the training mask types when their count matches the checkpoint, else zero planes."""
+    extra, types = conditioning_types(g, kind, mask_types)
+    if extra <= 0:
+        return None
+    if types is None:
+        return [np.zeros((extra,) + h.shape, np.float32) for h in hu_slices]
+    from .hip import ops
+    out = []
+    for h in hu_slices:
+        m = ops.anatomical_masks(torch.from_numpy(np.ascontiguousarray(h, np.float32)).to(device), types)
+        out.append(m[0].cpu().numpy())
+    return out
+
+
+@torch.no_grad()
+def translate_volume_device(soft_model, lung_model, raw_stored, slopes, intercepts,
+                            soft_range: Tuple[float, float], lung_range: Tuple[float, float], img_size: int,
+                            batch: int = 16, device="cuda", mask_types=MASK_TYPES, want_stored: bool = False):
+    """The translation of one NCCT series with both Generators and the HU-range merge, resident on
+    the device: what ``_conditioning`` + ``translate_slices`` + ``stored_from_output`` per model and
+    ``synthesize`` per slice compute, without a host round trip in between.
+
+    raw_stored: [D,H,W] int16 / uint16 host array (one upload); slopes / intercepts: one rescale
+    pair per slice.  HU and both [-1, 1] images come from the HU kernel, the masks from the mask
+    kernel on whole chunks, the resizes to and from img_size (when the slice size differs) from
+    modules/hip/slices.py, and the Generators run over chunks of exactly ``batch`` slices in series
+    order (the last one short), as translate_slices does: the f16x3 operand exponent is taken over
+    a whole call, so the result depends on the chunking.
+
+    Returns the merged values as a float32 [D,H,W] device tensor, the input of
+    ``smooth_volume_device``; with want_stored=True the tuple (merged, soft stored, lung stored),
+    the two stored-value series as int16 device tensors (the bits of a uint16 series)."""
+    from .hip import ops
+    from .hip import slices as S
+    raw = np.asarray(raw_stored)
+    if raw.dtype not in (np.int16, np.uint16):
+        raise TypeError(f"translate_volume_device: stored dtype {raw.dtype} (int16 or uint16 expected)")
+    if raw.ndim != 3 or raw.size == 0:
+        raise ValueError("translate_volume_device: [D,H,W] series required")
+    D, H, W = raw.shape
+    if len(slopes) != D or len(intercepts) != D:
+        raise ValueError("translate_volume_device: one slope/intercept per slice")
+    batch, size = int(batch), (int(img_size), int(img_size))
+    if batch < 1:
+        raise ValueError("translate_volume_device: batch must be positive")
+    unsigned = raw.dtype == np.uint16
+    if unsigned and not hasattr(torch, "uint16"):
+        raise RuntimeError("translate_volume_device: this torch has no uint16 tensors")
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        bits = torch.from_numpy(np.ascontiguousarray(raw).view(np.int16)).to(dev)
+        px = bits.view(torch.uint16) if unsigned else bits
+        f32 = lambda v: torch.tensor([float(x) for x in v], dtype=torch.float32).to(dev)
+        slope, inter = f32(slopes), f32(intercepts)
+        hu, img_soft = ops.hu_transform(px, slope, inter, soft_range[0], soft_range[1], soft=False)
+        _, img_lung = ops.hu_transform(px, slope, inter, lung_range[0], lung_range[1], soft=False, want_hu=False)
+        ys = []
+        for kind, model, img in (("soft_tissue", soft_model, img_soft), ("lung", lung_model, img_lung)):
+            extra, types = conditioning_types(model, kind, mask_types)
+            chunks = []
+            for i in range(0, D, batch):
+                x = S.resize_aa(img[i:i + batch, None], size)
+                if extra <= 0:
+                    out = model(x)
+                else:
+                    if types is None:
+                        m = torch.zeros((x.shape[0], extra) + size, dtype=torch.float32, device=dev)
+                    else:
+                        m = S.resize_nearest(ops.anatomical_masks(hu[i:i + batch], types), size)
+                    out = model(x, m)  # concat fused into the stem gather
+                chunks.append(S.resize_aa(out.float(), (H, W)))
+            ys.append(torch.cat(chunks).view(D, H, W))
+        so, lo, _, merged = S.translate_merge(bits, slope, inter, ys[0], ys[1], soft_range, lung_range,
+                                              unsigned=unsigned, want_soft=want_stored, want_lung=want_stored,
+                                              want_merged=False, want_f32=True)
+    return (merged, so, lo) if want_stored else merged
+
+
 def synthesize(raw_stored: np.ndarray, raw_hu: np.ndarray, soft_stored: np.ndarray, lung_stored: np.ndarray,
                soft_range: Tuple[float, float], lung_range: Tuple[float, float]) -> np.ndarray:
     """generate.py:212-236: start from the NCCT stored values and overwrite the pixels whose

@@ -643,6 +643,44 @@ int dcs_vol_merge(const void* raw, const void* soft, const void* lung, int store
                   const float* intercept, int D, int H, int W, float soft_lo, float soft_hi, float lung_lo,
                   float lung_hi, void* out, float* out_f32, void* stream);
 
+/* ---- slice series of the resident inference path (generate.py --pipeline resident:
+ *      modules/inference.py::stored_from_output + synthesize, torchvision Resize) ---- */
+#define DCS_RESIZE_MAX_TAPS 18 /* taps of one output sample of dcs_resize_aa (in/out <= 8) */
+
+/* Model outputs -> stored values -> HU-range merge in one pass over a [D][H][W] series.
+ *   y_soft, y_lung: the two Generators' outputs, float32 in [-1, 1]
+ *   raw: the NCCT stored values, stored_dtype DCS_VOL_I16 or DCS_VOL_U16; slope/intercept: device [D]
+ * Per element, in float32 and in the host's operation order (no fused multiply-add):
+ *   hu = ((y + 1) / 2) * span + lo;  px = (hu - intercept[z]) / slope[z]
+ *   stored = px cast to the stored dtype by truncation toward zero (numpy astype)
+ * with span = hi - lo formed by the caller.  Then dcs_vol_merge's rule on hu_raw = f32(raw) *
+ * slope[z] + intercept[z]: soft_lo <= hu_raw <= soft_hi takes the soft value, then lung_lo <=
+ * hu_raw <= lung_hi takes the lung value.  A px that does not fit the stored dtype is not pinned:
+ * numpy's cast is undefined there, and this kernel keeps the low 16 bits of the saturating
+ * float32 -> int32 conversion.
+ * Outputs, each optional (NULL = not written), at least one required: soft_stored, lung_stored and
+ * merged in the stored dtype; merged_f32 = the merged values as float32. */
+int dcs_vol_translate_merge(const void* raw, int stored_dtype, const float* slope, const float* intercept,
+                            const float* y_soft, const float* y_lung, int D, int H, int W, float soft_lo,
+                            float soft_hi, float soft_span, float lung_lo, float lung_hi, float lung_span,
+                            void* soft_stored, void* lung_stored, void* merged, float* merged_f32, void* stream);
+/* Antialiased bilinear resize (F.interpolate(mode="bilinear", align_corners=False, antialias=True))
+ * of NC planes [H][W] -> [oh][ow], separable: horizontal pass, then vertical pass.  The caller
+ * builds the weights (modules/hip/slices.py::aa_tables) and passes them as DEVICE tables, one set
+ * per axis: start[o] = first input sample of output o, count[o] <= taps its tap count,
+ * weights[o][taps] padded with zeros.  The kernels accumulate acc = acc + x * w from zero in tap
+ * order, in float32 without fused multiply-add; table entries are clamped into the input.
+ * An axis whose size does not change is skipped and its tables may be NULL; both sizes equal is
+ * DCS_E_INVALID (return the input instead), and so is in/out > 8 on either axis (more than
+ * DCS_RESIZE_MAX_TAPS taps).  tmp: [NC][H][ow] floats, required when both axes change. */
+int dcs_resize_aa(const float* in, float* out, float* tmp, int NC, int H, int W, int oh, int ow,
+                  const int32_t* x_start, const int32_t* x_count, const float* x_weights, int x_taps,
+                  const int32_t* y_start, const int32_t* y_count, const float* y_weights, int y_taps,
+                  void* stream);
+/* F.interpolate(mode="nearest") of NC planes: src = min(int(floorf(dst * float32(in / out))), in - 1)
+ * per axis; exact. */
+int dcs_resize_nearest(const float* in, float* out, int NC, int H, int W, int oh, int ow, void* stream);
+
 /* ---- evaluation metrics (calculate.py's MAE, PSNR, SSIM, EMD, texture similarity, cosine
  *      similarity and Euclidean distance; modules/metrics.py on the host) ----
  * a (target) and b (prediction): dense float32 [D][H][W] device volumes, x fastest.  Every result
