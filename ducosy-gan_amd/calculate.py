@@ -5,8 +5,8 @@
 
 It converts the VUE, STD and generated DICOM series of every patient to ``.npy`` stacks sorted by
 ImagePositionPatient[2], computes MAE, PSNR, SSIM (raw and normalised) for the three pairs and
-EMD, texture similarity, cosine similarity and Euclidean distance for STD against Generated,
-and writes the reference's files under ``<output_dir_root>/calculated``:
+EMD, texture similarity, cosine similarity and Euclidean distance (with --ms_ssim, MS-SSIM too)
+for STD against Generated, and writes the reference's files under ``<output_dir_root>/calculated``:
 ``data/{dataset}_{patient}_{category}.npy``, ``detail/{dataset}_{patient}_metrics.csv``,
 ``result_all_metrics.pkl`` and ``summary_statistics.csv``.
 
@@ -16,8 +16,13 @@ Differences from the reference, all deliberate:
     arithmetic fixed in modules/metrics.py;
   * patients run one after another in this process (no process pool: --num_workers is accepted
     and ignored);
-  * MS-SSIM and LPIPS need torchmetrics and lpips and are left empty, as the reference leaves
-    them without those libraries; the box and scatter plots need seaborn and are skipped;
+  * MS-SSIM is computed only with --ms_ssim (off by default, which keeps the files of earlier
+    runs unchanged), on either --device, from a restatement of torchmetrics' defaults
+    (modules/metrics.py::ms_ssim_levels; torchmetrics is not installed, so parity with the
+    reference's own numbers is unpinned); without the flag its column is empty.  It is defined
+    for slices of at least 176 x 176 and is empty below that, as in the reference;
+  * LPIPS needs the lpips library and its AlexNet weights and is left empty, as the reference
+    leaves it without them; the box and scatter plots need seaborn and are skipped;
   * nothing happens at import or while parsing arguments: no environment variable is set and no
     directory is created before the conversion starts.
 DICOM files are read with modules/dicom.py.
@@ -61,10 +66,12 @@ def get_args(argv=None):
     p.add_argument("--reset", action="store_true", help="Remove the calculation output directory first")
     p.add_argument("--mask", action="store_true", help="Calculate the metrics on the masked series")
     p.add_argument("--skip_convert", action="store_true", help="Reuse the .npy stacks of an earlier run")
-    p.add_argument("--use_gpu", action="store_true", help="Accepted for compatibility (LPIPS / MS-SSIM are not computed)")
+    p.add_argument("--use_gpu", action="store_true", help="Accepted for compatibility (LPIPS is not computed; see --device and --ms_ssim)")
     p.add_argument("--num_workers", type=int, default=1, help="Accepted for compatibility (patients run in sequence)")
     p.add_argument("--device", choices=["cpu", "cuda"], default="cpu",
                    help="cuda: compute the metrics with the HIP kernels; cpu: numpy / scipy on the host")
+    p.add_argument("--ms_ssim", action="store_true",
+                   help="Compute MS-SSIM of STD against Generated (slices of at least 176 x 176), on either --device")
     return p.parse_args(argv)
 
 
@@ -140,7 +147,7 @@ def convert(args):
     return out_dir, data_dir, tasks
 
 
-def process_patient(dataset, patient, data_dir, detail_dir, device):
+def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=False):
     """Metrics of one patient and its detail CSV; None when the STD or generated stack is missing."""
     path = lambda c: os.path.join(data_dir, f"{dataset}_{patient}_{c}.npy")
     if not (os.path.exists(path("std")) and os.path.exists(path("generated"))):
@@ -149,10 +156,10 @@ def process_patient(dataset, patient, data_dir, detail_dir, device):
         std, gen = np.load(path("std")), np.load(path("generated"))
         vue = np.load(path("vue")) if os.path.exists(path("vue")) else None
         if device is None:
-            patient_metrics, csv_data = M.evaluate_patient(std, gen, vue)
+            patient_metrics, csv_data = M.evaluate_patient(std, gen, vue, ms_ssim)
         else:
             from modules import metrics_gpu
-            patient_metrics, csv_data = metrics_gpu.evaluate_patient(std, gen, vue, device=device)
+            patient_metrics, csv_data = metrics_gpu.evaluate_patient(std, gen, vue, device=device, ms_ssim=ms_ssim)
         try:
             M.write_detail_csv(os.path.join(detail_dir, f"{dataset}_{patient}_metrics.csv"), csv_data, vue is not None)
         except Exception as e:
@@ -164,7 +171,7 @@ def process_patient(dataset, patient, data_dir, detail_dir, device):
         return None
 
 
-def calculate(out_dir, data_dir, tasks, device):
+def calculate(out_dir, data_dir, tasks, device, ms_ssim=False):
     print(f"\nCalculating metrics for generated images (device: {device or 'cpu'})...")
     result_path = os.path.join(out_dir, "result_all_metrics.pkl")
     detail_dir = os.path.join(out_dir, "detail")
@@ -180,7 +187,7 @@ def calculate(out_dir, data_dir, tasks, device):
         summary = {k: [] for k in M.METRICS}
         valid = 0
         for n, (dataset, patient) in enumerate(tasks, 1):
-            res = process_patient(dataset, patient, data_dir, detail_dir, device)
+            res = process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim)
             print(f"  [{n}/{len(tasks)}] {dataset} {patient}: {'done' if res is not None else 'skipped'}")
             if res is None:
                 continue
@@ -245,7 +252,7 @@ def main(argv=None):
     device = f"cuda:{args.gpu_id}" if args.device == "cuda" else None
     out_dir, data_dir, tasks = convert(args)
     if tasks:
-        calculate(out_dir, data_dir, tasks, device)
+        calculate(out_dir, data_dir, tasks, device, args.ms_ssim)
     else:
         print("No tasks found. Please check input directories and arguments.")
     summary_statistics(os.path.join(out_dir, "detail"),

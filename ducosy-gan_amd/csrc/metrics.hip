@@ -1,8 +1,9 @@
 // Evaluation metrics of calculate.py on gfx950 (modules/metrics.py on the host): MAE, PSNR, cosine
 // similarity and the min/max of a volume pair from one pass, per-slice SSIM, the Sobel texture
 // similarity, the per-slice normalised Euclidean distance and the L1 distance of two row-sorted
-// volumes (the Wasserstein-1 distance of EMD).  Dense float32 [D][H][W] volumes, x fastest; every
-// result is one float64 per slice.
+// volumes (the Wasserstein-1 distance of EMD), and the levels of MS-SSIM (the per-slice sums of one
+// level and the 2x2 pooling between levels).  Dense float32 [D][H][W] volumes, x fastest; every
+// result is float64 per slice.
 //
 // Arithmetic (the spec modules/metrics.py follows too): the reference's numpy elementwise
 // expressions stay in float32, one IEEE operation per step (a - b, its square, the (x - off) / div
@@ -295,6 +296,108 @@ __global__ void __launch_bounds__(MT) sobel_kernel(const float* __restrict__ a, 
     }
 }
 
+// One level of MS-SSIM (torchmetrics' defaults, restated in modules/metrics.py::ms_ssim_levels):
+// the sums of the SSIM map and of its contrast-structure factor over one TX x TY tile of the
+// interior (H-10) x (W-10) of slice z, whose 11x11 windows lie inside the image.  The tile and its
+// 10-pixel halo are staged in LDS; a thread owns one column of a strip of SR rows, walks down
+// SR + 10 input rows, filters x, y, x^2, y^2 and xy of each along the row once (taps in ascending
+// order, float64) and keeps the last eleven rows' values in registers, which the column filter
+// of eleven outputs reuses.  The window comes from the host as eleven doubles, so both paths
+// filter with the same bits.
+//   cs = (2 sxy + c2) / (sx2 + sy2 + c2),  sim = ((2 ux uy + c1)(2 sxy + c2)) / ((ux^2 + uy^2 + c1)(sx2 + sy2 + c2))
+// with sx2 = E[x^2] - ux^2 and so on (no N/(N-1) factor).  Writes {sum sim, sum cs} of the tile.
+constexpr int MSW = DCS_MET_MSSSIM_TAPS, MSH = MSW - 1;  // window taps and halo
+struct MsWin {
+    double g[MSW];
+};
+__global__ void __launch_bounds__(MT) msssim_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
+                                                    int ntx, int nty, MsWin win, double c1, double c2,
+                                                    double* __restrict__ ws) {
+    __shared__ float sa[TY + MSH][TX + MSH], sb[TY + MSH][TX + MSH];
+    __shared__ double red[MT / WAVE];
+    const unsigned ntile = (unsigned)(ntx * nty);
+    const int64_t z = blockIdx.x / ntile;
+    const int tile = (int)(blockIdx.x % ntile);
+    const int tx0 = (tile % ntx) * TX, ty0 = (tile / ntx) * TY;
+    const float* __restrict__ pa = a + z * H * W;
+    const float* __restrict__ pb = b + z * H * W;
+    for (int i = threadIdx.x; i < (TY + MSH) * (TX + MSH); i += MT) {
+        const int r = i / (TX + MSH), c = i % (TX + MSH);
+        const int y = ty0 + r, x = tx0 + c;
+        float va = 0.f, vb = 0.f;
+        if (y < H && x < W) {
+            va = pa[(int64_t)y * W + x];
+            vb = pb[(int64_t)y * W + x];
+        }
+        sa[r][c] = va;
+        sb[r][c] = vb;
+    }
+    __syncthreads();
+    const int Ho = H - MSH, Wo = W - MSH;
+    const int cx = threadIdx.x & (TX - 1), r0 = (int)(threadIdx.x / TX) * SR;
+    const bool col_ok = tx0 + cx < Wo;
+    double acc_sim = 0.0, acc_cs = 0.0;
+    if (ty0 + r0 < Ho) {  // wave-uniform: a strip is one wave
+        double ring[MSW][5];
+#pragma unroll
+        for (int i = 0; i < SR + MSH; ++i) {
+            double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0;
+#pragma unroll
+            for (int k = 0; k < MSW; ++k) {
+                const double x = (double)sa[r0 + i][cx + k], y = (double)sb[r0 + i][cx + k];
+                const double g = win.g[k];
+                m0 += g * x;
+                m1 += g * y;
+                m2 += g * (x * x);
+                m3 += g * (y * y);
+                m4 += g * (x * y);
+            }
+            ring[i % MSW][0] = m0, ring[i % MSW][1] = m1, ring[i % MSW][2] = m2, ring[i % MSW][3] = m3,
+                          ring[i % MSW][4] = m4;
+            if (i >= MSH) {
+                double s[5];
+#pragma unroll
+                for (int q = 0; q < 5; ++q) {
+                    s[q] = 0.0;
+#pragma unroll
+                    for (int j = 0; j < MSW; ++j) s[q] += win.g[j] * ring[(i - MSH + j) % MSW][q];
+                }
+                const double uxuy = s[0] * s[1], ux2 = s[0] * s[0], uy2 = s[1] * s[1];
+                const double upper = 2.0 * (s[4] - uxuy) + c2;
+                const double lower = (s[2] - ux2) + (s[3] - uy2) + c2;
+                const double cs = upper / lower;
+                const double sim = ((2.0 * uxuy + c1) * upper) / ((ux2 + uy2 + c1) * lower);
+                if (col_ok && ty0 + r0 + i - MSH < Ho) {
+                    acc_sim += sim;
+                    acc_cs += cs;
+                }
+            }
+        }
+    }
+    acc_sim = block_red<OP_ADD>(acc_sim, red);
+    acc_cs = block_red<OP_ADD>(acc_cs, red);
+    if (threadIdx.x == 0) {
+        double* out = ws + (int64_t)blockIdx.x * 2;
+        out[0] = acc_sim, out[1] = acc_cs;
+    }
+}
+
+// The next MS-SSIM level of both volumes: the 2x2 average with floor sizes (an odd last row or
+// column is dropped), float32(((a + b) + c) + d) * 0.25) with the sum in float64.
+__global__ void __launch_bounds__(MT) pool2_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
+                                                   int Ho, int Wo, int64_t n, float* __restrict__ oa,
+                                                   float* __restrict__ ob) {
+    const int64_t i = (int64_t)blockIdx.x * MT + threadIdx.x;
+    if (i >= n) return;
+    const int xo = (int)(i % Wo);
+    const int64_t t = i / Wo;
+    const int yo = (int)(t % Ho);
+    const int64_t z = t / Ho;
+    const int64_t src = (z * H + 2 * yo) * W + 2 * xo;
+    oa[i] = (float)(((((double)a[src] + (double)a[src + 1]) + (double)a[src + W]) + (double)a[src + W + 1]) * 0.25);
+    ob[i] = (float)(((((double)b[src] + (double)b[src + 1]) + (double)b[src + W]) + (double)b[src + W + 1]) * 0.25);
+}
+
 template <int VEC>
 __global__ void __launch_bounds__(MT) normalize_kernel(const float* __restrict__ x, int64_t nvec, Aff t,
                                                        float* __restrict__ out) {
@@ -440,6 +543,41 @@ extern "C" int dcs_met_sobel_ts(const float* a, const float* b, int D, int H, in
     hipLaunchKernelGGL(sobel_kernel, dim3((unsigned)((int64_t)D * ntx * nty)), dim3(MT), 0, s, a, b, H, W, ntx, nty,
                        static_cast<double*>(ws));
     return fold(static_cast<const double*>(ws), D, ntx * nty, 3, (OP_MAX << 2) | (OP_MAX << 4), out, s, "met_sobel_ts");
+}
+
+extern "C" int dcs_met_msssim_level(const float* a, const float* b, int D, int H, int W, const double* window, double c1,
+                                    double c2, double* out, void* ws, size_t ws_bytes, void* stream) {
+    if (H < MSW || W < MSW) return fail(DCS_E_INVALID, "met_msssim_level: the 11x11 window exceeds the image");
+    if (int rc = pair_args("met_msssim_level", a, b, D, H, W, out, ws, ws_bytes, tiles(H - MSH, W - MSH), 2)) return rc;
+    if (!window) return fail(DCS_E_INVALID, "met_msssim_level: null window");
+    MsWin win;
+    for (int k = 0; k < MSW; ++k) {
+        win.g[k] = window[k];
+        if (!(win.g[k] - win.g[k] == 0.0)) return fail(DCS_E_INVALID, "met_msssim_level: the window must be finite");
+    }
+    if (!(c1 - c1 == 0.0) || !(c2 - c2 == 0.0) || c1 < 0.0 || c2 < 0.0)
+        return fail(DCS_E_INVALID, "met_msssim_level: c1 and c2 must be finite and not negative");
+    const int ntx = (int)cdiv(W - MSH, TX), nty = (int)cdiv(H - MSH, TY);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(msssim_kernel, dim3((unsigned)((int64_t)D * ntx * nty)), dim3(MT), 0, s, a, b, H, W, ntx, nty, win,
+                       c1, c2, static_cast<double*>(ws));
+    // out[z] = {sum sim, sum cs}; the caller divides by (H-10)(W-10)
+    return fold(static_cast<const double*>(ws), D, ntx * nty, 2, OP_ADD, out, s, "met_msssim_level");
+}
+
+extern "C" int dcs_met_pool2(const float* a, const float* b, float* out_a, float* out_b, int D, int H, int W,
+                             void* stream) {
+    if (!a || !b || !out_a || !out_b) return fail(DCS_E_INVALID, "met_pool2: null pointer");
+    if (!dims_ok(D, H, W) || H < 2 || W < 2) return fail(DCS_E_INVALID, "met_pool2: bad dimensions");
+    if (!aligned(a, 4) || !aligned(b, 4) || !aligned(out_a, 4) || !aligned(out_b, 4))
+        return fail(DCS_E_INVALID, "met_pool2: misaligned pointer");
+    if (out_a == out_b || out_a == a || out_a == b || out_b == a || out_b == b)
+        return fail(DCS_E_INVALID, "met_pool2: the outputs must not alias each other or the inputs");
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t n = (int64_t)D * Ho * Wo;
+    hipLaunchKernelGGL(pool2_kernel, dim3((unsigned)cdiv(n, MT)), dim3(MT), 0, as_stream(stream), a, b, H, W, Ho, Wo, n,
+                       out_a, out_b);
+    return check_launch("met_pool2");
 }
 
 extern "C" int dcs_met_normalize(const float* x, int64_t n, float off, float div, float* out, void* stream) {

@@ -21,6 +21,7 @@ VOL_F32, VOL_F64, VOL_I16, VOL_U16 = 0, 1, 2, 3  # DCS_VOL_* dtypes
 VOL_MAX_RADIUS, VOL_MAX_MEDIAN, VOL_MINMAX_PARTS = 16, 9, 1024
 RESIZE_MAX_TAPS = 18  # DCS_RESIZE_MAX_TAPS
 MET_NSTATS, MET_TILE_X, MET_TILE_Y, MET_PAIR_CHUNK = 9, 64, 32, 8192  # DCS_MET_*
+MET_MSSSIM_TAPS = 11
 
 
 class ConvDesc(ctypes.Structure):
@@ -191,6 +192,9 @@ SIGNATURES = {
     "dcs_met_ed": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "dcs_met_sorted_l1": (c_int, [P, P, c_int, c_int, c_int, POINTER(c_float), P, P, c_size_t, P]),
     "dcs_met_normalize": (c_int, [P, c_int64, c_float, c_float, P, P]),
+    "dcs_met_msssim_level": (c_int, [P, P, c_int, c_int, c_int, POINTER(c_double), c_double, c_double, P, P, c_size_t,
+                                     P]),
+    "dcs_met_pool2": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
 }
 
 

@@ -120,6 +120,35 @@ def sorted_l1(a: torch.Tensor, b: torch.Tensor, affine=None) -> torch.Tensor:
     return out
 
 
+def msssim_level_sums(a: torch.Tensor, b: torch.Tensor, window: Sequence[float], c1: float, c2: float) -> torch.Tensor:
+    """float64 [D,2]: the sums of the SSIM map and of its contrast-structure factor over the
+    (H-10) x (W-10) windows inside every slice of one MS-SSIM level (the means divide by that
+    count).  window: the eleven float64 taps of the separable filter."""
+    a, b = _pair(a, b, "msssim_level")
+    D, H, W = a.shape
+    if len(window) != lib.MET_MSSSIM_TAPS:
+        raise ValueError(f"msssim_level: a window of {lib.MET_MSSSIM_TAPS} taps is required")
+    if H < lib.MET_MSSSIM_TAPS or W < lib.MET_MSSSIM_TAPS:
+        raise ValueError("msssim_level: the 11x11 window exceeds the image")
+    ws, n = _workspace(a)
+    out = torch.empty((D, 2), dtype=torch.float64, device=a.device)
+    win = (ctypes.c_double * lib.MET_MSSSIM_TAPS)(*[float(v) for v in window])
+    lib.call("dcs_met_msssim_level", _p(a), _p(b), D, H, W, win, float(c1), float(c2), _p(out), _p(ws), n, _stream())
+    return out
+
+
+def pool2(a: torch.Tensor, b: torch.Tensor):
+    """The 2x2 averages of both volumes, float32 [D,H//2,W//2] each (the sum of four in float64)."""
+    a, b = _pair(a, b, "pool2")
+    D, H, W = a.shape
+    if H < 2 or W < 2:
+        raise ValueError("pool2: both sides of a slice must be at least 2")
+    oa = torch.empty((D, H // 2, W // 2), dtype=torch.float32, device=a.device)
+    ob = torch.empty_like(oa)
+    lib.call("dcs_met_pool2", _p(a), _p(b), _p(oa), _p(ob), D, H, W, _stream())
+    return oa, ob
+
+
 def normalize(x: torch.Tensor, off: float, div: float) -> torch.Tensor:
     """(x - off) / div in float32, zeros where div is 0."""
     x = _vol(x, "normalize")

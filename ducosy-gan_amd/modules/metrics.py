@@ -14,8 +14,11 @@ on numpy's float32 pairwise sums, so the arithmetic is fixed here, and modules/m
   * skimage's structural_similarity and sobel are restated in float64 on the float32 samples;
   * min and max are exact.
 
-ms_ssim and lpips need torchmetrics and lpips; they return ``(nan, [])`` as the reference does
-without those libraries.
+ms_ssim restates torchmetrics' MultiScaleStructuralSimilarityIndexMeasure(data_range=1.0) with
+its defaults (rules at ``ms_ssim_levels``).  torchmetrics is not installed, so parity with the
+reference's own output is unpinned; the two paths here agree with each other and with a direct
+float64 formula (tests/test_cpu_msssim.py, tests/test_gpu_msssim.py).  lpips needs the lpips
+library and returns ``(nan, [])`` as the reference does without it.
 """
 from __future__ import annotations
 
@@ -31,6 +34,15 @@ ADVANCED = ("ms_ssim", "lpips", "emd", "ts", "cs", "ed")
 METRICS = BASIC + ADVANCED
 EPS32 = np.float32(1e-8)
 SSIM_WIN = 7
+# MS-SSIM: torchmetrics' defaults.  The 11-tap gaussian (sigma 1.5) normalised to sum 1 in float64;
+# the device path passes these eleven doubles to its kernel, so both filter with the same bits.
+MS_SSIM_BETAS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+MS_SSIM_TAPS = 11
+MS_SSIM_MIN_SIDE = 176   # the fifth level must hold one window: 176 -> 88 -> 44 -> 22 -> 11
+MS_SSIM_C1, MS_SSIM_C2 = 0.01 ** 2, 0.03 ** 2
+_g = np.exp(-((np.arange(MS_SSIM_TAPS, dtype=np.float64) - 5) / 1.5) ** 2 / 2)
+MS_SSIM_WINDOW = _g / _g.sum()
+MS_SSIM_WINDOW.setflags(write=False)
 
 
 def _f32(img) -> np.ndarray:
@@ -113,12 +125,113 @@ def ssim(img1, img2) -> Result:
     return float(np.mean(vals)), vals
 
 
+def ms_ssim_defined(shape) -> bool:
+    return len(shape) == 3 and min(shape[1:]) >= MS_SSIM_MIN_SIDE
+
+
+def ms_ssim_renormalize(x) -> np.ndarray:
+    """``(x - min) / (max - min + 1e-8)`` over the volume in float32 (the reference's step before
+    the metric); the identity on the output of normalize(), where 1 + 1e-8 rounds to 1."""
+    x = _f32(x)
+    mn, mx = x.min(), x.max()
+    return (x - mn) / ((mx - mn) + EPS32)
+
+
+def ms_ssim_pool(x: np.ndarray) -> np.ndarray:
+    """2x2 average with floor sizes: float32(((a + b) + c) + d) * 0.25), the sum in float64."""
+    h, w = x.shape[1] // 2 * 2, x.shape[2] // 2 * 2
+    v = x[:, :h, :w].astype(np.float64)
+    s = ((v[:, 0::2, 0::2] + v[:, 0::2, 1::2]) + v[:, 1::2, 0::2]) + v[:, 1::2, 1::2]
+    return (s * 0.25).astype(np.float32)
+
+
+def ms_ssim_pyramid(img1, img2) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """The five float32 levels of both re-normalised volumes."""
+    a, b = _pair(img1, img2)
+    if not ms_ssim_defined(a.shape):
+        raise ValueError(f"ms_ssim: both sides of a slice must be at least {MS_SSIM_MIN_SIDE}")
+    levels = [(ms_ssim_renormalize(a), ms_ssim_renormalize(b))]
+    for _ in range(len(MS_SSIM_BETAS) - 1):
+        levels.append((ms_ssim_pool(levels[-1][0]), ms_ssim_pool(levels[-1][1])))
+    return levels
+
+
+def _ms_ssim_filter(v: np.ndarray) -> np.ndarray:
+    """The separable window along W, then along H; only the windows inside the image are kept
+    (torchmetrics pads by 5 with reflection and crops 5 again, which leaves exactly these)."""
+    r = MS_SSIM_TAPS // 2
+    f = correlate1d(correlate1d(v, MS_SSIM_WINDOW, axis=1, mode="reflect"), MS_SSIM_WINDOW, axis=0, mode="reflect")
+    return f[r:v.shape[0] - r, r:v.shape[1] - r]
+
+
+def ms_ssim_level_slice(s1: np.ndarray, s2: np.ndarray) -> Tuple[float, float]:
+    """The float64 means of the SSIM map and of its contrast-structure factor over the interior
+    (h-10) x (w-10) of one slice of one level; no N/(N-1) factor."""
+    x, y = s1.astype(np.float64), s2.astype(np.float64)
+    ux, uy = _ms_ssim_filter(x), _ms_ssim_filter(y)
+    vx = _ms_ssim_filter(x * x) - ux * ux
+    vy = _ms_ssim_filter(y * y) - uy * uy
+    vxy = _ms_ssim_filter(x * y) - ux * uy
+    upper, lower = 2 * vxy + MS_SSIM_C2, vx + vy + MS_SSIM_C2
+    cs_map = upper / lower
+    sim = ((2 * (ux * uy) + MS_SSIM_C1) * upper) / ((ux * ux + uy * uy + MS_SSIM_C1) * lower)
+    return float(np.mean(sim, dtype=np.float64)), float(np.mean(cs_map, dtype=np.float64))
+
+
+def ms_ssim_levels(img1, img2) -> np.ndarray:
+    """float64 [5][D][2]: per level and slice the mean of the SSIM map and of its contrast-structure
+    factor, before the clamp.  The rules, torchmetrics' defaults restated:
+
+      * both volumes are re-normalised (ms_ssim_renormalize);
+      * five levels; the next is the 2x2 average of the last with floor sizes (ms_ssim_pool),
+        stored as float32;
+      * at every level the 11-tap gaussian (MS_SSIM_WINDOW) filters x, y, x^2, y^2 and xy in
+        float64 on the float32 samples, over the windows that lie inside the image;
+      * cs = (2 sxy + C2) / (sx2 + sy2 + C2), sim = ((2 ux uy + C1)(2 sxy + C2)) /
+        ((ux^2 + uy^2 + C1)(sx2 + sy2 + C2)), C1 = 0.01^2, C2 = 0.03^2.
+    Raises ValueError below 176 pixels on a side, where the fifth level cannot hold a window."""
+    out = [[ms_ssim_level_slice(s1, s2) for s1, s2 in zip(x, y)] for x, y in ms_ssim_pyramid(img1, img2)]
+    return np.array(out, dtype=np.float64)
+
+
+def ms_ssim_from_levels(levels) -> List[float]:
+    """Per slice ``prod_{i<4} cs_i^beta_i * sim_4^beta_4`` of the level means clamped below at 0
+    (normalize='relu'), in float64 (shared with the device path)."""
+    lv = np.maximum(np.asarray(levels, dtype=np.float64), 0.0)
+    last = len(MS_SSIM_BETAS) - 1
+    val = lv[last, :, 0] ** MS_SSIM_BETAS[last]
+    for i in range(last - 1, -1, -1):
+        val = lv[i, :, 1] ** MS_SSIM_BETAS[i] * val
+    return val.tolist()
+
+
+def ms_ssim_result(vals: Sequence[float]) -> Result:
+    """The reference returns the batch value repeated for every slice."""
+    agg = float(np.mean(vals))
+    return agg, [agg] * len(vals)
+
+
+def ms_ssim_slices(img1, img2) -> List[float]:
+    """MS-SSIM of every slice; [] where it is not defined (a side below 176)."""
+    a, b = _pair(img1, img2)
+    if not ms_ssim_defined(a.shape):
+        return []
+    return ms_ssim_from_levels(ms_ssim_levels(a, b))
+
+
 def ms_ssim(img1, img2) -> Result:
-    return float("nan"), []
+    """torchmetrics' MultiScaleStructuralSimilarityIndexMeasure(data_range=1.0) of the re-normalised
+    volumes: the mean over the slices, repeated for every slice.  ``(nan, [])`` below 176 pixels on
+    a side, as the reference gives where torchmetrics refuses the image."""
+    vals = ms_ssim_slices(img1, img2)
+    return ms_ssim_result(vals) if vals else (float("nan"), [])
 
 
 def lpips(img1, img2) -> Result:
     return float("nan"), []
+
+
+_ms_ssim = ms_ssim   # evaluate_pair's switch carries the function's name
 
 
 def emd(img1, img2) -> Result:
@@ -184,14 +297,16 @@ def ed(img1, img2) -> Result:
     return float(np.mean(vals)), vals
 
 
-def evaluate_pair(target, pred, advanced: bool = True) -> Dict[str, Result]:
-    """The basic metrics on the raw and the normalised volumes, and the advanced ones if asked."""
+def evaluate_pair(target, pred, advanced: bool = True, ms_ssim: bool = False) -> Dict[str, Result]:
+    """The basic metrics on the raw and the normalised volumes, and the advanced ones if asked;
+    MS-SSIM is computed only with ``ms_ssim=True`` and is ``(nan, [])`` otherwise."""
+    ms = _ms_ssim if ms_ssim else lpips   # not asked for: empty, as lpips is
     t, p = _pair(target, pred)
     tn, pn = normalize(t), normalize(p)
     out = {"mae": mae(t, p), "psnr": psnr(t, p), "ssim": ssim(t, p),
            "mae_norm": mae(tn, pn), "psnr_norm": psnr(tn, pn), "ssim_norm": ssim(tn, pn)}
     if advanced:
-        out.update({"ms_ssim": ms_ssim(tn, pn), "lpips": lpips(tn, pn), "emd": emd(t, p), "ts": ts(t, p),
+        out.update({"ms_ssim": ms(tn, pn), "lpips": lpips(tn, pn), "emd": emd(t, p), "ts": ts(t, p),
                     "cs": cs(t, p), "ed": ed(t, p)})
     return out
 
@@ -200,10 +315,11 @@ def pair_names(has_vue: bool) -> List[str]:
     return ["STD_vs_Generated"] + (["VUE_vs_STD", "VUE_vs_Generated"] if has_vue else [])
 
 
-def collect_patient(pair_fn, std, gen, vue=None):
+def collect_patient(pair_fn, std, gen, vue=None, ms_ssim: bool = False):
     """The per-patient driver both paths share: the basic metrics for every pair, the advanced
     ones for STD against Generated; series are cut to the shortest.  ``pair_fn(target, pred,
-    advanced)`` is evaluate_pair of the host or of the device module.  Returns (patient_metrics,
+    advanced)`` is evaluate_pair of the host or of the device module; with ``ms_ssim`` it is
+    called with ``ms_ssim=True`` as well.  Returns (patient_metrics,
     csv_data): per metric the list of aggregates and the list of per-slice lists, one per pair."""
     n = min(len(v) for v in (std, gen, vue) if v is not None)
     std, gen = std[:n], gen[:n]
@@ -213,15 +329,16 @@ def collect_patient(pair_fn, std, gen, vue=None):
         pairs += [(vue, std, False), (vue, gen, False)]
     patient = {k: [] for k in METRICS}
     per_slice = {k: [] for k in METRICS}
+    kw = {"ms_ssim": True} if ms_ssim else {}
     for targ, pred, adv in pairs:
-        for k, (agg, lst) in pair_fn(targ, pred, adv).items():
+        for k, (agg, lst) in pair_fn(targ, pred, adv, **kw).items():
             patient[k].append(agg)
             per_slice[k].append(lst)
     return patient, per_slice
 
 
-def evaluate_patient(std, gen, vue=None):
-    return collect_patient(evaluate_pair, std, gen, vue)
+def evaluate_patient(std, gen, vue=None, ms_ssim: bool = False):
+    return collect_patient(evaluate_pair, std, gen, vue, ms_ssim)
 
 
 def detail_header(has_vue: bool) -> List[str]:

@@ -12,7 +12,11 @@ docstring, so the two paths agree to the rounding of float64 sums taken in diffe
   * SSIM, the Sobel texture similarity and the Euclidean distance take one pass each; EMD sorts
     the raw rows with torch.sort (plumbing) and takes one more pass.  The float32 normalisation
     ``(x - min) / div`` with div > 0 is monotone, so sorting before it gives the same sorted
-    normalised samples as sorting after it.
+    normalised samples as sorting after it;
+  * MS-SSIM, computed only when asked for, re-normalises both volumes, pools them four times
+    (one launch per level for the pair) and takes one pass per level; the level means come to
+    the host and the powers and the product run there, shared with the host path.  Parity with
+    torchmetrics is unpinned (modules/metrics.py).
 
 Only per-slice float64 vectors come back to the host.  No CPU fallback: host tensors raise.
 """
@@ -140,7 +144,46 @@ def ed(img1, img2) -> Result:
     return _ed(img1, img2, PairStats(img1, img2))
 
 
-ms_ssim, lpips = M.ms_ssim, M.lpips
+def ms_ssim_pyramid(img1, img2):
+    """modules/metrics.py::ms_ssim_pyramid on the device: the five float32 levels of both
+    re-normalised volumes, bit for bit the host's."""
+    a, b = K._pair(img1, img2, "ms_ssim")
+    if not M.ms_ssim_defined(a.shape):
+        raise ValueError(f"ms_ssim: both sides of a slice must be at least {M.MS_SSIM_MIN_SIDE}")
+    st = PairStats(a, b)
+    # div = range + 1e-8f is never 0, so the kernel's zero branch is not taken
+    levels = [(K.normalize(a, float(st.amin), float(_rng32(st.amin, st.amax) + M.EPS32)),
+               K.normalize(b, float(st.bmin), float(_rng32(st.bmin, st.bmax) + M.EPS32)))]
+    for _ in range(len(M.MS_SSIM_BETAS) - 1):
+        levels.append(K.pool2(*levels[-1]))
+    return levels
+
+
+def ms_ssim_levels(img1, img2) -> np.ndarray:
+    """modules/metrics.py::ms_ssim_levels: float64 [5][D][2], the only values that come to the
+    host besides the extrema of the re-normalisation."""
+    sums, counts = [], []
+    for x, y in ms_ssim_pyramid(img1, img2):
+        counts.append((x.shape[1] - 10) * (x.shape[2] - 10))
+        sums.append(K.msssim_level_sums(x, y, M.MS_SSIM_WINDOW, M.MS_SSIM_C1, M.MS_SSIM_C2))
+    return torch.stack(sums).cpu().numpy() / np.array(counts, np.float64)[:, None, None]
+
+
+def ms_ssim_slices(img1, img2) -> list:
+    a, b = K._pair(img1, img2, "ms_ssim")
+    if not M.ms_ssim_defined(a.shape):
+        return []
+    return M.ms_ssim_from_levels(ms_ssim_levels(a, b))
+
+
+def ms_ssim(img1, img2) -> Result:
+    """modules/metrics.py::ms_ssim; ``(nan, [])`` below 176 pixels on a side, without a launch."""
+    vals = ms_ssim_slices(img1, img2)
+    return M.ms_ssim_result(vals) if vals else (float("nan"), [])
+
+
+lpips = M.lpips
+_ms_ssim = ms_ssim
 
 
 def to_device(x, device) -> torch.Tensor:
@@ -150,7 +193,7 @@ def to_device(x, device) -> torch.Tensor:
     return x.to(device=device, dtype=torch.float32)
 
 
-def evaluate_pair(target, pred, device, advanced: bool = True) -> Dict[str, Result]:
+def evaluate_pair(target, pred, device, advanced: bool = True, ms_ssim: bool = False) -> Dict[str, Result]:
     """modules/metrics.py::evaluate_pair on ``device``."""
     t, p = to_device(target, device), to_device(pred, device)
     _check_window(t)
@@ -161,15 +204,19 @@ def evaluate_pair(target, pred, device, advanced: bool = True) -> Dict[str, Resu
            "mae_norm": stn.mae(), "psnr_norm": stn.psnr(),
            "ssim_norm": _ssim(t, p, float(_rng32(stn.bmin, stn.bmax)), aff)}
     if advanced:
-        out.update({"ms_ssim": ms_ssim(None, None), "lpips": lpips(None, None), "emd": _emd(t, p, st),
+        ms = lpips(None, None)   # not asked for: empty, as lpips is
+        if ms_ssim:              # on materialised normalize() volumes, as the host path does
+            ms = _ms_ssim(K.normalize(t, aff[0], aff[1]), K.normalize(p, aff[2], aff[3]))
+        out.update({"ms_ssim": ms, "lpips": lpips(None, None), "emd": _emd(t, p, st),
                     "ts": _ts(t, p), "cs": st.cs(), "ed": _ed(t, p, st)})
     return out
 
 
-def evaluate_patient(std, gen, vue=None, device: Optional[object] = "cuda"):
+def evaluate_patient(std, gen, vue=None, device: Optional[object] = "cuda", ms_ssim: bool = False):
     """modules/metrics.py::evaluate_patient; ``device=None`` runs the host module, anything else
     uploads every series once and keeps the work on that device."""
     if device is None:
-        return M.evaluate_patient(std, gen, vue)
+        return M.evaluate_patient(std, gen, vue, ms_ssim)
     up = lambda v: None if v is None else to_device(v, device)
-    return M.collect_patient(lambda t, p, adv: evaluate_pair(t, p, device, adv), up(std), up(gen), up(vue))
+    return M.collect_patient(lambda t, p, adv, **kw: evaluate_pair(t, p, device, adv, **kw), up(std), up(gen), up(vue),
+                             ms_ssim)

@@ -681,7 +681,7 @@ int dcs_resize_aa(const float* in, float* out, float* tmp, int NC, int H, int W,
  * per axis; exact. */
 int dcs_resize_nearest(const float* in, float* out, int NC, int H, int W, int oh, int ow, void* stream);
 
-/* ---- evaluation metrics (calculate.py's MAE, PSNR, SSIM, EMD, texture similarity, cosine
+/* ---- evaluation metrics (calculate.py's MAE, PSNR, SSIM, MS-SSIM, EMD, texture similarity, cosine
  *      similarity and Euclidean distance; modules/metrics.py on the host) ----
  * a (target) and b (prediction): dense float32 [D][H][W] device volumes, x fastest.  Every result
  * is float64 per slice.  Arithmetic: the float32 elementwise steps of the numpy expressions
@@ -721,6 +721,19 @@ int dcs_met_sorted_l1(const float* a, const float* b, int D, int H, int W, const
                       void* ws, size_t ws_bytes, void* stream);
 /* out = (x - off) / div in float32, 0 where div == 0 (calculate.py's normalize) */
 int dcs_met_normalize(const float* x, int64_t n, float off, float div, float* out, void* stream);
+/* One level of MS-SSIM (torchmetrics' MultiScaleStructuralSimilarityIndexMeasure defaults, restated
+ * in modules/metrics.py): out[z][0..1] = the SUMS of the SSIM map and of its contrast-structure
+ * factor (2 sxy + c2) / (sx2 + sy2 + c2) over the (H-10) x (W-10) windows that lie inside slice z;
+ * the means divide by (H-10)(W-10).  window: HOST array of the DCS_MET_MSSSIM_TAPS float64 taps of
+ * the separable filter (x, y, x^2, y^2, xy in float64 along W, then along H); no N/(N-1) factor.
+ * H, W >= 11; c1, c2 >= 0; dcs_met_workspace_size bytes of workspace suffice. */
+#define DCS_MET_MSSSIM_TAPS 11
+int dcs_met_msssim_level(const float* a, const float* b, int D, int H, int W, const double* window, double c1,
+                         double c2, double* out, void* ws, size_t ws_bytes, void* stream);
+/* The next MS-SSIM level of both volumes, [D][H/2][W/2] (an odd last row or column is dropped):
+ * out[i][j] = float32((((x[2i][2j] + x[2i][2j+1]) + x[2i+1][2j]) + x[2i+1][2j+1]) * 0.25), the sum
+ * in float64.  H, W >= 2; the outputs alias nothing. */
+int dcs_met_pool2(const float* a, const float* b, float* out_a, float* out_b, int D, int H, int W, void* stream);
 
 /* small utilities */
 int dcs_scale_add(float* y, const float* x, float a, int64_t n, void* stream); /* y += a*x */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Host against device timing of calculate.py's per-patient metrics (modules/metrics_gpu.py::evaluate_patient).
 
-    python scripts/bench_metrics.py [--shape 128x512x512] [--reps 5] [--host_reps 5] [--skip_host]
+    python scripts/bench_metrics.py [--shape 128x512x512] [--reps 5] [--host_reps 5] [--skip_host] [--ms_ssim]
 
 One synthetic patient from modules/phantom.py (STD, a generated series = STD + rounded N(0, 20),
 a VUE series) goes through
@@ -14,6 +14,13 @@ a VUE series) goes through
     share of the 8 TB/s HBM peak.
 The two paths' results are compared at the bars of tests/test_gpu_metrics.py.  Prints progress
 lines and, last, one JSON line.
+
+--ms_ssim turns the MS-SSIM switch of evaluate_patient on in every leg above (its column is then
+compared at 1e-9 absolute, the bar of tests/test_gpu_msssim.py), and adds under "ms_ssim" the
+metric alone on the STD / generated pair: host time, device time end to end and on resident
+volumes, and the event time of the level kernel at each of the five levels and of the pooling
+kernel between them (the level kernel reads both volumes once: 8 bytes per voxel of its level;
+the pooling kernel reads both and writes a quarter: 10 bytes per input voxel).
 """
 import argparse
 import json
@@ -91,8 +98,25 @@ def kernel_times(std, gen, reps):
     return out
 
 
+def ms_ssim_times(std, gen, reps):
+    """Event time of the MS-SSIM kernels on the resident pair, level by level."""
+    out = {}
+    levels = G.ms_ssim_pyramid(std, gen)
+    for i, (x, y) in enumerate(levels):
+        runs = {f"msssim_level{i}": (lambda: K.msssim_level_sums(x, y, M.MS_SSIM_WINDOW, M.MS_SSIM_C1, M.MS_SSIM_C2),
+                                     8 * x.numel())}
+        if i + 1 < len(levels):
+            runs[f"pool2_level{i}"] = (lambda: K.pool2(x, y), 10 * x.numel())
+        for name, (fn, nbytes) in runs.items():
+            ms = _median_ms(fn, reps)
+            out[name] = {"ms": round(ms, 4), "shape": "x".join(str(v) for v in x.shape),
+                         "algorithmic_GBps": round(nbytes / ms / 1e6, 1),
+                         "share_of_hbm_peak": round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)}
+    return out
+
+
 def _agree(got, want):
-    worst = {"rel": 0.0, "ssim_abs": 0.0}
+    worst = {"rel": 0.0, "ssim_abs": 0.0, "ms_ssim_abs": 0.0}
     ok = True
     for k in M.METRICS:
         for gl, wl in zip(got[1][k], want[1][k]):
@@ -102,11 +126,13 @@ def _agree(got, want):
             if not f.any():
                 continue
             err = np.abs(g[f] - w[f])
-            if k.startswith("ssim"):
+            if k == "ms_ssim":
+                worst["ms_ssim_abs"] = max(worst["ms_ssim_abs"], float(err.max()))
+            elif k.startswith("ssim"):
                 worst["ssim_abs"] = max(worst["ssim_abs"], float(err.max()))
             else:
                 worst["rel"] = max(worst["rel"], float((err / np.maximum(np.abs(w[f]), 1e-300)).max()))
-    return bool(ok and worst["rel"] <= 1e-10 and worst["ssim_abs"] <= 1e-10), worst
+    return bool(ok and worst["rel"] <= 1e-10 and worst["ssim_abs"] <= 1e-10 and worst["ms_ssim_abs"] <= 1e-9), worst
 
 
 def main():
@@ -116,6 +142,7 @@ def main():
     ap.add_argument("--host_reps", type=int, default=5)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--skip_host", action="store_true", help="device times only (no comparison)")
+    ap.add_argument("--ms_ssim", action="store_true", help="with MS-SSIM in every leg, and its own times")
     a = ap.parse_args()
     dev = torch.device(a.device)
     shape = tuple(int(x) for x in a.shape.split("x"))
@@ -125,12 +152,12 @@ def main():
     std, gen, vue = patient(shape)
     print(f"phantom patient {shape} in {time.perf_counter() - t0:.1f} s", flush=True)
     res = {"metric": "evaluate_patient_seconds", "device": torch.cuda.get_device_name(dev), "shape": a.shape,
-           "host_threads": threads}
+           "host_threads": threads, "with_ms_ssim": a.ms_ssim}
 
     def device_run():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = G.evaluate_patient(std, gen, vue, device=dev)
+        out = G.evaluate_patient(std, gen, vue, device=dev, ms_ssim=a.ms_ssim)
         torch.cuda.synchronize()
         return time.perf_counter() - t0, out
 
@@ -143,11 +170,24 @@ def main():
     res["device_end_to_end_s"] = round(statistics.median(times), 4)
 
     ds, dg, dv = (G.to_device(v, dev) for v in (std, gen, vue))
-    resident = lambda: G.evaluate_patient(ds, dg, dv, device=dev)
+    resident = lambda: G.evaluate_patient(ds, dg, dv, device=dev, ms_ssim=a.ms_ssim)
     resident()
     torch.cuda.synchronize()
     res["device_resident_ms"] = round(statistics.median(_events(resident) for _ in range(a.reps)), 3)
     res["kernels"] = kernel_times(ds, dg, a.reps)
+    if a.ms_ssim:
+        def alone():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            val = G.ms_ssim(G.to_device(std, dev), G.to_device(gen, dev))
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, val
+        alone()
+        runs = [alone() for _ in range(a.reps)]
+        ms = {"device_end_to_end_s": round(statistics.median(r[0] for r in runs), 4), "device_value": runs[-1][1][0],
+              "device_resident_ms": round(_median_ms(lambda: G.ms_ssim(ds, dg), a.reps), 3)}
+        res["kernels"].update(ms_ssim_times(ds, dg, a.reps))
+        res["ms_ssim"] = ms
     del ds, dg, dv
     print("device:", json.dumps({k: res[k] for k in ("device_end_to_end_s", "device_resident_ms")}), flush=True)
 
@@ -155,7 +195,7 @@ def main():
         times = []
         for i in range(a.host_reps + 1):
             t0 = time.perf_counter()
-            want = G.evaluate_patient(std, gen, vue, device=None)
+            want = G.evaluate_patient(std, gen, vue, device=None, ms_ssim=a.ms_ssim)
             dt = time.perf_counter() - t0
             print(f"host run {i}{' (warm-up)' if i == 0 else ''}: {dt:.2f} s", flush=True)
             if i:
@@ -164,6 +204,14 @@ def main():
         res["agree"], res["worst_error"] = _agree(got, want)
         res["speedup_end_to_end"] = round(res["host_s"] / res["device_end_to_end_s"], 1)
         res["speedup_resident"] = round(res["host_s"] * 1e3 / res["device_resident_ms"], 1)
+        if a.ms_ssim:
+            times = []
+            for i in range(a.host_reps + 1):
+                t0 = time.perf_counter()
+                val = M.ms_ssim(std, gen)
+                times.append(time.perf_counter() - t0)
+            res["ms_ssim"].update({"host_s": round(statistics.median(times[1:]), 3), "host_value": val[0],
+                                   "abs_error": abs(val[0] - res["ms_ssim"]["device_value"])})
     print(json.dumps(res))
     if not a.skip_host and not res["agree"]:
         sys.exit(1)

@@ -95,6 +95,56 @@ int main() {
     EXPECT(dcs_met_normalize(fa, 1ll << 38, 0.f, 1.f, fb, nullptr) == DCS_E_INVALID);
     EXPECT(dcs_met_normalize(fa, 8, nan, 1.f, fb, nullptr) == DCS_E_INVALID);
     EXPECT(dcs_met_normalize(fa, 8, 0.f, inf, fb, nullptr) == DCS_E_INVALID);
+    // MS-SSIM level: the window, its taps, c1 / c2, two partials per tile
+    double win[DCS_MET_MSSSIM_TAPS], badwin[DCS_MET_MSSSIM_TAPS];
+    for (int k = 0; k < DCS_MET_MSSSIM_TAPS; ++k) win[k] = badwin[k] = 1.0 / DCS_MET_MSSSIM_TAPS;
+    const double c1 = 1e-4, c2 = 9e-4;
+    const size_t need11 = dcs_met_workspace_size(2, 11, 11);
+    EXPECT(need11 >= 2 * 2 * sizeof(double) && need11 <= sizeof(ws));
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 10, 11, win, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 10, win, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, -11, 11, win, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 0, 11, 11, win, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, big, big, big, win, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(nullptr, fb, 2, 11, 11, win, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, win, c1, c2, nullptr, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, win, c1, c2, out, nullptr, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, nullptr, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(reinterpret_cast<float*>(reinterpret_cast<char*>(fa) + 2), fb, 2, 11, 11, win, c1, c2, out,
+                                ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, win, c1, c2, out, ws, 2 * 2 * sizeof(double) - 1, nullptr) ==
+           DCS_E_WORKSPACE);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, win, c1, c2, out, ws, 0, nullptr) == DCS_E_WORKSPACE);
+    badwin[10] = (double)nan;
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, badwin, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    badwin[10] = (double)inf, badwin[0] = 0.0;
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, badwin, c1, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, win, (double)nan, c2, out, ws, need11, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_msssim_level(fa, fb, 2, 11, 11, win, c1, -1.0, out, ws, need11, nullptr) == DCS_E_INVALID);
+    // the existing workspace size covers two partials per tile of the (H-10) x (W-10) interior
+    for (int d = 1; d < 40; d += 7)
+        for (int h = 11; h < 700; h += 53)
+            for (int w = 11; w < 9000; w += 997) {
+                const size_t tile = (size_t)d * ((h - 10 + 31) / 32) * ((w - 10 + 63) / 64) * 2 * sizeof(double);
+                EXPECT(dcs_met_workspace_size(d, h, w) >= tile);
+            }
+    // 2x2 pooling
+    static float oa[8], ob[8];
+    EXPECT(dcs_met_pool2(nullptr, fb, oa, ob, 2, 2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, nullptr, oa, ob, 2, 2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, nullptr, ob, 2, 2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, nullptr, 2, 2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, ob, 2, 1, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, ob, 2, 2, 1, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, ob, 0, 2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, ob, 2, -2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, ob, big, big, big, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, ob, 1 << 20, 512, 512, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, reinterpret_cast<float*>(reinterpret_cast<char*>(oa) + 1), ob, 2, 2, 2, nullptr) ==
+           DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, oa, 2, 2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, fa, ob, 2, 2, 2, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_pool2(fa, fb, oa, fb, 2, 2, 2, nullptr) == DCS_E_INVALID);
     std::printf(failures ? "metrics host check: %d FAILED\n" : "metrics host check: ok\n", failures);
     return failures ? EXIT_FAILURE : EXIT_SUCCESS;
 }
