@@ -18,7 +18,11 @@ Differences from the reference, all deliberate:
   * --pipeline resident (generate_synthesis) runs both stages in one pass per patient: stored
     NCCT pixels go up once, HU transform, masks, resizes, both Generators, the output -> stored
     value map, the merge and the smoothing stay on the GPU (csrc/slices.hip, csrc/volume.hip), the
-    int16 volume comes down once; no working series is written unless --write_working is given.
+    int16 volume comes down once; no working series is written unless --write_working is given;
+  * --apply_diffmap runs the reference's difference-map stage (commented out in its synthesis()):
+    the normal-map U-Net of --nmodel_path predicts a contrast difference map from the NCCT HU
+    series (modules/nmodel, csrc/unet.hip) and apply_diffmap adds it to the merged volume before
+    the smoothing; --save_diff keeps the map as diff.npy in the patient's working directory.
 DICOM reading/writing uses modules/dicom.py (pydicom is not installed in this image).
 """
 import argparse
@@ -38,6 +42,9 @@ from modules.inference import (MASK_TYPES, _conditioning, hu_from_stored, normal
                                smooth_volume, smooth_volume_device, stored_from_output, synthesize,
                                synthesize_volume, translate_slices, translate_volume_device)
 from modules.model import Generator  # noqa: E402
+from modules.nmodel import load_model, predict_volume  # noqa: E402
+from modules.postprocess import apply_diffmap  # noqa: E402
+from modules.postprocess_gpu import apply_diffmap_device  # noqa: E402
 
 
 def load_generator(path, device, num_residual_blocks=9):
@@ -62,6 +69,13 @@ def _model_args(args, soft_tissue_args, lung_args):
         lung_args = argparse.Namespace(model_path=args.model_path_lung, hu_min=args.lung_hu_min,
                                        hu_max=args.lung_hu_max)
     return soft_tissue_args, lung_args
+
+
+def _load_nmodel(args, device):
+    """The difference-map U-Net when --apply_diffmap is given, else None."""
+    if not getattr(args, "apply_diffmap", False):
+        return None
+    return load_model(args.nmodel_path, device)[0]
 
 
 def generate(args, soft_tissue_args=None, lung_args=None):
@@ -118,6 +132,7 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
     from modules import dicom
     sa, la = _model_args(args, soft_tissue_args, lung_args)
     post_dev = f"cuda:{args.gpu_id}" if getattr(args, "postprocess_device", "cpu") == "cuda" else None
+    nmodel = _load_nmodel(args, torch.device(f"cuda:{args.gpu_id}"))
     for dataset_name in args.dataset_names:
         working_dir = os.path.join(args.working_dir_root, dataset_name)
         output_dir = os.path.join(args.output_dir_root, dataset_name)
@@ -126,9 +141,12 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
             if not all(lists) or len({len(x) for x in lists}) != 1:
                 print(f"Skipping {patient_dir}: missing or mismatched slices")
                 continue
-            merged, series, rescale = [], [], []
+            merged, series, rescale, raw_hu_series = [], [], [], []
             for rp, sp, lp in zip(*lists):
                 raw, st, lg = dicom.dcmread(rp), dicom.dcmread(sp), dicom.dcmread(lp)
+                if nmodel is not None:
+                    raw_hu_series.append(hu_from_stored(raw.pixel_array, getattr(raw, "RescaleSlope", 1),
+                                                        getattr(raw, "RescaleIntercept", 0)))
                 if post_dev is not None:
                     series.append((raw.pixel_array, st.pixel_array, lg.pixel_array))
                     rescale.append((getattr(raw, "RescaleSlope", 1), getattr(raw, "RescaleIntercept", 0)))
@@ -142,6 +160,16 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
                 on_dev = synthesize_volume(raw_v, [a for a, _ in rescale], [b for _, b in rescale], soft_v, lung_v,
                                            (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max), device=post_dev,
                                            keep_on_device=True)
+            if nmodel is not None:  # the difference-map stage: after the merge, before the smoothing
+                diff = predict_volume(nmodel, np.stack(raw_hu_series), f"cuda:{args.gpu_id}")
+                if getattr(args, "save_diff", False):
+                    np.save(os.path.join(patient_dir, "diff.npy"), diff)
+                thr = getattr(args, "diffmap_threshold", 8)
+                if post_dev is not None:
+                    on_dev = apply_diffmap_device(on_dev, torch.from_numpy(diff).to(post_dev), thr)
+                else:
+                    merged = apply_diffmap(np.stack(merged), diff, thr)
+            if post_dev is not None:
                 vol = smooth_volume(on_dev, device=post_dev)
             else:
                 vol = smooth_volume(merged)
@@ -185,6 +213,8 @@ def generate_synthesis(args, soft_tissue_args=None, lung_args=None):
     device = torch.device(f"cuda:{args.gpu_id}")
     soft = load_generator(sa.model_path, device)
     lung = load_generator(la.model_path, device)
+    nmodel = _load_nmodel(args, device)
+    save_diff = nmodel is not None and bool(getattr(args, "save_diff", False))
     batch = int(getattr(args, "slice_batch", 16))
     write_working = bool(getattr(args, "write_working", False))
     soft_range, lung_range = (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max)
@@ -213,13 +243,19 @@ def generate_synthesis(args, soft_tissue_args=None, lung_args=None):
             if write_working:
                 for d in work.values():
                     os.makedirs(d, exist_ok=True)
-            for idxs in groups.values():
+            for gi, idxs in enumerate(groups.values()):
                 raw = np.stack([pixels[i] for i in idxs])
+                stage = {} if nmodel is None else dict(nmodel=nmodel, want_diff=save_diff,
+                                                       diffmap_threshold=getattr(args, "diffmap_threshold", 8))
                 res = translate_volume_device(
                     soft, lung, raw, [getattr(dcms[i], "RescaleSlope", 1) for i in idxs],
                     [getattr(dcms[i], "RescaleIntercept", 0) for i in idxs], soft_range, lung_range,
-                    args.img_size, batch, device, want_stored=write_working)
-                merged = res[0] if write_working else res
+                    args.img_size, batch, device, want_stored=write_working, **stage)
+                merged = res[0] if (write_working or save_diff) else res
+                if save_diff:  # one file per slice format; a uniform series writes diff.npy
+                    os.makedirs(os.path.join(working_dir, patient), exist_ok=True)
+                    name = "diff.npy" if len(groups) == 1 else f"diff_{gi}.npy"
+                    np.save(os.path.join(working_dir, patient, name), res[-1].cpu().numpy())
                 vol = smooth_volume_device(merged).cpu().numpy()
                 if write_working:
                     series = {k: t.cpu().numpy().view(raw.dtype) for k, t in (("soft_tissue", res[1]), ("lung", res[2]))}
@@ -268,6 +304,16 @@ def get_args(argv=None):
                         "with --skip_convert the staged synthesis() runs on the working series either way")
     p.add_argument("--write_working", action="store_true",
                    help="--pipeline resident: also write the raw / soft_tissue / lung working series")
+    p.add_argument("--apply_diffmap", action="store_true",
+                   help="run the difference-map stage: the U-Net of --nmodel_path predicts a contrast difference map "
+                        "from the NCCT series and apply_diffmap adds it to the merged volume before the smoothing")
+    p.add_argument("--nmodel_path", type=str, default="./checkpoints/Normal_Map_Unet.pth",
+                   help="--apply_diffmap: checkpoint of the normal-map U-Net (UNet3D or UNet3DLight)")
+    p.add_argument("--diffmap_threshold", type=float, default=8,
+                   help="--apply_diffmap: difference-map values below this are dropped")
+    p.add_argument("--save_diff", action="store_true",
+                   help="--apply_diffmap: write the predicted difference map as diff.npy into the patient's working "
+                        "directory")
     return p.parse_args(argv)
 
 

@@ -195,6 +195,11 @@ SIGNATURES = {
     "dcs_met_msssim_level": (c_int, [P, P, c_int, c_int, c_int, POINTER(c_double), c_double, c_double, P, P, c_size_t,
                                      P]),
     "dcs_met_pool2": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "dcs_unet_normalize_hu": (c_int, [P, c_int64, c_int, P, P]),
+    "dcs_unet_affine_relu_pool": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, P]),
+    "dcs_unet_upsample2_pad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
+    "dcs_unet_out_diffmap": (c_int, [P, P, P, P, c_float, c_int64, c_int, c_float, P, P, P, P]),
+    "dcs_unet_apply_diffmap": (c_int, [P, c_int64, c_float, P, P, P]),
 }
 
 

@@ -99,7 +99,8 @@ def _conditioning(g, kind, hu_slices, device, mask_types=MASK_TYPES):
 @torch.no_grad()
 def translate_volume_device(soft_model, lung_model, raw_stored, slopes, intercepts,
                             soft_range: Tuple[float, float], lung_range: Tuple[float, float], img_size: int,
-                            batch: int = 16, device="cuda", mask_types=MASK_TYPES, want_stored: bool = False):
+                            batch: int = 16, device="cuda", mask_types=MASK_TYPES, want_stored: bool = False,
+                            nmodel=None, diffmap_threshold=8, want_diff: bool = False):
     """The translation of one NCCT series with both Generators and the HU-range merge, resident on
     the device: what ``_conditioning`` + ``translate_slices`` + ``stored_from_output`` per model and
     ``synthesize`` per slice compute, without a host round trip in between.
@@ -113,7 +114,12 @@ def translate_volume_device(soft_model, lung_model, raw_stored, slopes, intercep
 
     Returns the merged values as a float32 [D,H,W] device tensor, the input of
     ``smooth_volume_device``; with want_stored=True the tuple (merged, soft stored, lung stored),
-    the two stored-value series as int16 device tensors (the bits of a uint16 series)."""
+    the two stored-value series as int16 device tensors (the bits of a uint16 series).
+
+    nmodel: a modules/nmodel U-Net; the difference-map stage then runs between the merge and the
+    return: the U-Net over the ``hu`` tensor that is already here, ending in the kernel that adds the
+    thresholded uint8 map into ``merged`` (modules/nmodel/inference.py::apply_predicted_diffmap_device),
+    no transfer.  want_diff=True appends the float difference map (device) to the result."""
     from .hip import ops
     from .hip import slices as S
     raw = np.asarray(raw_stored)
@@ -157,7 +163,14 @@ def translate_volume_device(soft_model, lung_model, raw_stored, slopes, intercep
         so, lo, _, merged = S.translate_merge(bits, slope, inter, ys[0], ys[1], soft_range, lung_range,
                                               unsigned=unsigned, want_soft=want_stored, want_lung=want_stored,
                                               want_merged=False, want_f32=True)
-    return (merged, so, lo) if want_stored else merged
+        if nmodel is None:
+            return (merged, so, lo) if want_stored else merged
+        from .nmodel.inference import apply_predicted_diffmap_device
+        diff = apply_predicted_diffmap_device(nmodel, hu, merged, diffmap_threshold, want_diff=want_diff)
+    res = (merged, so, lo) if want_stored else (merged,)
+    if want_diff:
+        res += (diff,)
+    return res if len(res) > 1 else merged
 
 
 def synthesize(raw_stored: np.ndarray, raw_hu: np.ndarray, soft_stored: np.ndarray, lung_stored: np.ndarray,

@@ -124,6 +124,16 @@ def postprocess_ct_volume_device(vol, method="gaussian3d", enhance_sharpness=Tru
     return out
 
 
+def apply_diffmap_device(vol, diff, threshold=8):
+    """modules/postprocess.py::apply_diffmap on the device for a caller that already holds a
+    difference map: float32 device tensors of one shape -> a new float32 device tensor equal to
+    ``vol + (diff with values below threshold zeroed).astype(uint8)``; ``diff`` is left unchanged
+    (csrc/unet.hip).  No host fallback."""
+    from .hip import unet as U
+    with torch.cuda.device(vol.device):
+        return U.apply_diffmap(vol, diff, threshold)
+
+
 def postprocess_ct_volume_gpu(volume, method="gaussian3d", enhance_sharpness=True, hu_threshold=750, device="cuda",
                               **kwargs):
     """postprocess_ct_volume on ``device``: [slices, H, W] numpy array or device tensor -> int16

@@ -735,6 +735,48 @@ int dcs_met_msssim_level(const float* a, const float* b, int D, int H, int W, co
  * in float64.  H, W >= 2; the outputs alias nothing. */
 int dcs_met_pool2(const float* a, const float* b, float* out_a, float* out_b, int D, int H, int W, void* stream);
 
+/* ---- difference-map stage (modules/nmodel: the normal-map U-Net run one slice at a time, then
+ *      modules/postprocess.py::apply_diffmap) ----
+ * Activations are NHWC float32.  The U-Net's 3x3 convolutions run on dcs_conv_rows; these are the
+ * passes between them.  scale / shift: the eval-mode BatchNorm folded per channel (device [C],
+ * scale of either sign).  Float32 arithmetic without fused multiply-add; vector stores only, no
+ * atomics, results bit-identical from run to run.  Arguments are checked on the host before any
+ * launch (DCS_E_INVALID). */
+/* out[i * cstride] = ((clip(hu[i], -1024, 3071) + 1024) / 4095) * 2 - 1 (modules/nmodel's
+ * normalize_hu, bit for bit).  cstride 1: dense; cstride 4: pixels of 4 channels, channels 1..3
+ * written as zero (the first convolution's 16-byte source). */
+int dcs_unet_normalize_hu(const float* hu, int64_t n, int cstride, float* out, void* stream);
+/* a = relu(y * scale[c] + shift[c]) of y [N][H][W][C], C % 4 == 0, read once:
+ *   skip[((n*H + h)*W + w) * skip_cstride + c] = a   (skip_cstride >= C, % 4 == 0: the leading
+ *       channels of a concatenated tensor, or C for a dense one)
+ *   pooled [N][H/2][W/2][C] = the 2x2 maximum of a (floor sizes: an odd last row / column is dropped);
+ *       H, W >= 2. */
+int dcs_unet_affine_relu_pool(const float* y, const float* scale, const float* shift, int N, int H, int W, int C,
+                              float* skip, int skip_cstride, float* pooled, void* stream);
+/* Bilinear x2 upsample with align_corners=True of x [N][h][w][C] (C % 4 == 0), placed inside an
+ * Ho x Wo map (Ho >= 2h, Wo >= 2w) with (Ho - 2h) / 2 zero rows before it and the rest after, the
+ * same split along x:  out[((n*Ho + Y)*Wo + X) * out_cstride + c], out_cstride >= C, % 4 == 0
+ * (pass the pointer of the first channel slot behind the skip).  With scale / shift (both or
+ * neither) the source is read as relu(x * scale[c] + shift[c]).  A 1-pixel source axis repeats
+ * that pixel.  Source coordinate: float32(o) * (float32(in - 1) / float32(2 in - 1)), as ATen. */
+int dcs_unet_upsample2_pad(const float* x, const float* scale, const float* shift, int N, int h, int w, int C,
+                           int Ho, int Wo, float* out, int out_cstride, void* stream);
+/* The U-Net's tail and apply_diffmap in one pass over P pixels of y [P][C] (C % 4 == 0, <= 256):
+ *   o = sum_c relu(y[p][c] * scale[c] + shift[c]) * w[c] + bias     (1x1 convolution: c ascending;
+ *       for C = 32, 64, 128, 256 per group of 16 channels, the group sums added pairwise)
+ *   d = ((o + 1) / 2) * 4000                                         (denormalize_diff)
+ *   diff[p] = d                     when diff != NULL
+ *   m = d < threshold ? 0 : d;  vol_out[p] = vol_in[p] + float32(uint8(m))   when vol_in != NULL
+ * uint8(m): truncation to a 32-bit integer (saturating), low 8 bits kept, as numpy's astype on the
+ * host for every m below 2^31.  vol_out may alias vol_in; at least one output is required. */
+int dcs_unet_out_diffmap(const float* y, const float* scale, const float* shift, const float* w, float bias,
+                         int64_t P, int C, float threshold, const float* vol_in, float* vol_out, float* diff,
+                         void* stream);
+/* apply_diffmap for a difference map that already exists: vol_out[i] = vol_in[i] +
+ * float32(uint8(diff[i] < threshold ? 0 : diff[i])); diff is not modified; vol_out may alias vol_in. */
+int dcs_unet_apply_diffmap(const float* diff, int64_t n, float threshold, const float* vol_in, float* vol_out,
+                           void* stream);
+
 /* small utilities */
 int dcs_scale_add(float* y, const float* x, float a, int64_t n, void* stream); /* y += a*x */
 /* out = x * (*s) with s a device scalar (loss backward without a host sync) */

@@ -18,7 +18,9 @@ algorithm moves over that time; ``generators_only_s`` is the two Generators' for
 chunks with inputs already on the device, the part both legs share.  The int16 results are compared with np.array_equal when --size equals --img_size (the
 staged path's ATen resizes differ from the resize kernel in the last bits otherwise, which a
 truncating cast can turn into off-by-one stored values).  Prints ``identical: true/false`` and one
-JSON line.
+JSON line.  --apply_diffmap adds a third leg, the resident path with the difference-map stage
+(a seeded UNet3DLight base 16, or --nmodel full32 for UNet3D base 32; modules/nmodel), and reports it
+as ``resident_diffmap_s`` next to ``resident_s``.
 """
 import argparse
 import json
@@ -54,8 +56,9 @@ def staged(models, raw, slopes, inters, img_size, batch, dev):
     return smooth_volume(on_dev, device=dev)
 
 
-def resident(models, raw, slopes, inters, img_size, batch, dev):
-    merged = translate_volume_device(models[0], models[1], raw, slopes, inters, SOFT, LUNG, img_size, batch, dev)
+def resident(models, raw, slopes, inters, img_size, batch, dev, nmodel=None):
+    merged = translate_volume_device(models[0], models[1], raw, slopes, inters, SOFT, LUNG, img_size, batch, dev,
+                                     nmodel=nmodel)
     return smooth_volume_device(merged).cpu().numpy()
 
 
@@ -136,6 +139,8 @@ def main():
     ap.add_argument("--slice_batch", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--apply_diffmap", action="store_true", help="also time the resident path with the difference-map stage")
+    ap.add_argument("--nmodel", choices=["light16", "full32"], default="light16")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_generate.py needs a GPU")
@@ -146,6 +151,10 @@ def main():
     torch.manual_seed(0)
     models = (Generator(3, 9).to(dev).eval(), Generator(2, 9).to(dev).eval())
     legs = {"staged": staged, "resident": resident}
+    if a.apply_diffmap:
+        from modules.nmodel import UNet3D, UNet3DLight
+        nmodel = (UNet3DLight(base_channels=16) if a.nmodel == "light16" else UNet3D(base_channels=32)).to(dev).eval()
+        legs["resident_diffmap"] = lambda *args: resident(*args, nmodel=nmodel)
     times = {k: [] for k in legs}
     outs = {}
     for rep in range(a.reps + 1):            # rep 0 is the warm-up of both legs at the full shape
@@ -160,6 +169,11 @@ def main():
            "staged_all_s": [round(t, 4) for t in times["staged"]],
            "resident_all_s": [round(t, 4) for t in times["resident"]]}
     res["staged_over_resident"] = round(res["staged_s"] / res["resident_s"], 3)
+    if a.apply_diffmap:
+        res["nmodel"] = a.nmodel
+        res["resident_diffmap_s"] = round(min(times["resident_diffmap"]), 4)
+        res["resident_diffmap_all_s"] = [round(t, 4) for t in times["resident_diffmap"]]
+        res["diffmap_stage_s"] = round(res["resident_diffmap_s"] - res["resident_s"], 4)
     same = bool(np.array_equal(outs["staged"], outs["resident"]))
     res["identical"] = same
     if not same:
