@@ -200,6 +200,18 @@ SIGNATURES = {
     "dcs_unet_upsample2_pad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
     "dcs_unet_out_diffmap": (c_int, [P, P, P, P, c_float, c_int64, c_int, c_float, P, P, P, P]),
     "dcs_unet_apply_diffmap": (c_int, [P, c_int64, c_float, P, P, P]),
+    "dcs_unet_bn_stats_workspace_size": (c_size_t, [c_int64, c_int]),
+    "dcs_unet_bn_stats": (c_int, [P, c_int64, c_int, P, P, c_float, c_float, c_int, P, P, P, P, P, P, P, c_size_t, P]),
+    "dcs_unet_bn_relu_backward_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dcs_unet_bn_relu_backward_sums": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P,
+                                               P, c_size_t, P]),
+    "dcs_unet_bn_relu_backward_apply": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P,
+                                                P]),
+    "dcs_unet_l1_out_workspace_size": (c_size_t, [c_int64, c_int]),
+    "dcs_unet_l1_out": (c_int, [P, P, P, P, P, P, c_int64, c_int, c_float, P, P, P, P, c_size_t, P]),
+    "dcs_unet_upsample2_pad_backward": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "dcs_unet_sumsq_workspace_size": (c_size_t, [c_int64]),
+    "dcs_unet_sumsq": (c_int, [P, c_int64, c_float, P, P, c_size_t, P]),
 }
 
 

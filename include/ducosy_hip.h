@@ -777,6 +777,59 @@ int dcs_unet_out_diffmap(const float* y, const float* scale, const float* shift,
 int dcs_unet_apply_diffmap(const float* diff, int64_t n, float threshold, const float* vol_in, float* vol_out,
                            void* stream);
 
+/* ---- training the normal-map U-Net on depth-1 patches (modules/hip/unet_train.py) ----
+ * The passes between the convolutions of a training step.  Activations are NHWC float32, C % 4 == 0.
+ * Every reduction is two-stage with a fixed order (float64 partials per block, added in block
+ * order; no atomics): the same inputs give the same bits from run to run.  ws: 8-byte aligned. */
+/* BatchNorm in training mode over the M = N*H*W values per channel of y [M][C] (M >= 2, C <= 1024):
+ *   mean[c], invstd[c] = 1 / sqrt(biased variance + eps)          (from float64 sums)
+ *   scale[r*C + c] = gamma[c] * invstd[c], shift[r*C + c] = beta[c] - mean[c] * scale, r < nrep
+ *       (the pair dcs_conv_rows' prologue, dcs_unet_affine_relu_pool and dcs_unet_upsample2_pad read)
+ *   running_mean = (1 - momentum) * running_mean + momentum * mean
+ *   running_var  = (1 - momentum) * running_var + momentum * variance * M / (M - 1)   (both or NULL) */
+size_t dcs_unet_bn_stats_workspace_size(int64_t M, int C);
+int dcs_unet_bn_stats(const float* y, int64_t M, int C, const float* gamma, const float* beta, float eps,
+                      float momentum, int nrep, float* scale, float* shift, float* mean, float* invstd,
+                      float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
+/* Backward of a = relu(y * scale + shift) with batch statistics, y [N][H][W][C]:
+ *   g = da * [y * scale + shift > 0],  xhat = (y - mean) * invstd
+ *   sums:  dbeta[c] = sum g,  dgamma[c] = sum g * xhat
+ *   apply: dy = scale[c] * (g - dbeta[c] / M - xhat * dgamma[c] / M)      (scale = gamma * invstd)
+ * The gradient da reaching a comes in one of three forms:
+ *   A  da[((n*H + h)*W + w) * da_cstride + c]: a channel slice of a wider tensor (pass the pointer
+ *      of its first channel; da_cstride >= C, % 4 == 0);  dpool = dout = wout = NULL
+ *   B  A plus dpool [N][H/2][W/2][C], the gradient of the 2x2 max pool of a, added at the first
+ *      maximum of each window in row-major order (recomputed from y; an odd last row / column is in
+ *      no window);  H, W >= 2
+ *   C  da[p][c] = dout[p] * wout[c] (the 1x1 output projection; da = dpool = NULL); sums also writes
+ *      dwout[c] = sum_p dout[p] * a[p][c] and dbias[0] = sum_p dout[p]. */
+size_t dcs_unet_bn_relu_backward_workspace_size(int N, int H, int W, int C);
+int dcs_unet_bn_relu_backward_sums(const float* da, int da_cstride, const float* dpool, const float* dout,
+                                   const float* wout, const float* y, const float* scale, const float* shift,
+                                   const float* mean, const float* invstd, int N, int H, int W, int C, float* dgamma,
+                                   float* dbeta, float* dwout, float* dbias, void* ws, size_t ws_bytes, void* stream);
+int dcs_unet_bn_relu_backward_apply(const float* da, int da_cstride, const float* dpool, const float* dout,
+                                    const float* wout, const float* y, const float* scale, const float* shift,
+                                    const float* mean, const float* invstd, int N, int H, int W, int C,
+                                    const float* dgamma, const float* dbeta, float* dy, void* stream);
+/* The training tail over P pixels of y [P][C] (C <= 256):
+ *   o[p] = sum_c relu(y[p][c] * scale[c] + shift[c]) * wout[c] + bias[0]   (written when o != NULL)
+ *   loss[0] = gscale * sum_p |o[p] - target[p]| / P
+ *   dout[p] = gscale * sign(o[p] - target[p]) / P,  sign(0) = 0 */
+size_t dcs_unet_l1_out_workspace_size(int64_t P, int C);
+int dcs_unet_l1_out(const float* y, const float* scale, const float* shift, const float* wout, const float* bias,
+                    const float* target, int64_t P, int C, float gscale, float* o, float* dout, float* loss, void* ws,
+                    size_t ws_bytes, void* stream);
+/* Adjoint of dcs_unet_upsample2_pad: dx [N][h][w][C] from the gradient of the padded Ho x Wo map,
+ * dcat[((n*Ho + Y)*Wo + X) * cstride + c] (pass the pointer of the first upsampled channel).  A
+ * gather in ascending output order with the forward's own weights. */
+int dcs_unet_upsample2_pad_backward(const float* dcat, int cstride, int N, int h, int w, int C, int Ho, int Wo,
+                                    float* dx, void* stream);
+/* out[0] = sqrt(sum g[i]^2), out[1] = min(1, clip / (out[0] + 1e-6)) (1 for clip <= 0): the
+ * coefficient of clip_grad_norm_, left on the device for dcs_scale_dev. */
+size_t dcs_unet_sumsq_workspace_size(int64_t n);
+int dcs_unet_sumsq(const float* g, int64_t n, float clip, float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* small utilities */
 int dcs_scale_add(float* y, const float* x, float a, int64_t n, void* stream); /* y += a*x */
 /* out = x * (*s) with s a device scalar (loss backward without a host sync) */
