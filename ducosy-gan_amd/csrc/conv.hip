@@ -37,9 +37,6 @@ constexpr int MMA_BF16P = 2;
 constexpr int MMA_F16X3 = 7;
 // f16 (DCS_MMA_F16): the f16x3 staging with the hi planes only, one product (hi*hi) per fragment
 constexpr int MMA_F16 = 8;
-#ifndef DCS_BF16_BUFGATHER
-#define DCS_BF16_BUFGATHER 1  // branch-free buffer-descriptor gather in the bf16 rows pass
-#endif
 
 // bf16 LDS rows of the rows pass: 32 k of hi (+ 32 k of lo for bf16x3) + 8 pad elements;
 // 80-B / 144-B pitches keep the per-lane 16-B fragment reads conflict-free.
@@ -110,83 +107,13 @@ __device__ __forceinline__ void split4x3(const float4& a, bf16x4& hi, bf16x4& mi
 
 constexpr int BK = 32;
 constexpr int NT = 256;
-#ifndef DCS_X6_BK
-#define DCS_X6_BK 16
-#endif
-#ifndef DCS_TAG2
-#define DCS_TAG2 1  // TAG-2 instances (no prologue / epilogue activation) for the generic x6 / f16x3 passes
-#endif
-#ifndef DCS_WGRAD_WIN
-#define DCS_WGRAD_WIN 1  // f16x3 residual weight gradient on the rolling-window kernel (conv_win.hip)
-#endif
-#ifndef DCS_WGRAD_X6
-#define DCS_WGRAD_X6 1  // bf16x6 weight-gradient kernel in the bf16x6 mode
-#endif
-#ifndef DCS_WGRAD_X6_CO64
-#define DCS_WGRAD_X6_CO64 1  // ... also for 64 output channels in the fp16 modes (128-row tile, half masked): f16x3 up2 at bs 16
-                             // 2.15 ms vs 2.48 ms f32 (bf16x6 was 3.49 ms: off there), profiles/r03d
-#endif
-#ifndef DCS_X6_BN64
-#define DCS_X6_BN64 1  // bf16x6 rows also for 64-column tiles
-#endif
-#ifndef DCS_X6_V4
-#define DCS_X6_V4 1  // bf16x6 rows also for the 4-channel NHWC gather (stem, PatchGAN layer 0)
-#endif
-#ifndef DCS_X6_PIPE
-#define DCS_X6_PIPE 1  // bf16x6 rows: global loads two k-tiles ahead (two register sets)
-#endif
-#ifndef DCS_X6_SELGATHER
-#define DCS_X6_SELGATHER 1  // bf16x6 rows: gather address by selects, no exec-mask branch
-#endif
-#ifndef DCS_X6_STORE_FIRST
-#define DCS_X6_STORE_FIRST 1  // bf16x6 rows: stage the next tile before folding the chain
-#endif
-#ifndef DCS_KSLICE_ALL
-#define DCS_KSLICE_ALL 1  // bf16x6 rows: slice-major K walk for every 16-channel-aligned source
-#endif
-#ifndef DCS_X6_SGB
-#define DCS_X6_SGB 5  // bf16x6 residual rows: VALU instructions scheduled after each MFMA (0 = compiler)
-#endif
-#ifndef DCS_WGRAD_SGB
-#define DCS_WGRAD_SGB 5  // bf16x6 weight gradient: VALU instructions scheduled after each MFMA
-#endif
-#ifndef DCS_X6_SGB0
-#define DCS_X6_SGB0 0  // ... the same for the other bf16x6 rows kernels
-#endif
-#ifndef DCS_BF16P
-#define DCS_BF16P 1  // half-precision residual convs on the x6 pipeline (48 k per barrier)
-#endif
-#ifndef DCS_BF16P_ROWS
-#define DCS_BF16P_ROWS 1  // the residual rows passes too (else the plain bf16 rows kernel)
-#endif
-#ifndef DCS_BF16P_BM256
-#define DCS_BF16P_BM256 1  // ... on 256-row tiles where they divide the pixels
-#endif
-#ifndef DCS_WGRAD_REDUCE_UNROLL
-#define DCS_WGRAD_REDUCE_UNROLL 8
-#endif
-#ifndef DCS_X6_OCC
-#define DCS_X6_OCC 2  // bf16x6 rows: workgroups per CU the register budget is sized for
-#endif
-#ifndef DCS_H3_NSUB
-#define DCS_H3_NSUB 2  // f16x3 rows, 128-column tiles: 16-k sub-tiles per barrier (64-column tiles: 1)
-#endif
-#ifndef DCS_WGRAD_X6_V4
-#define DCS_WGRAD_X6_V4 1  // fp16 modes: 4-channel-source weight gradients (stem, PatchGAN layer 0) on the x6 kernel
-#endif
-#ifndef DCS_TAG4
-#define DCS_TAG4 1  // the Generator stem's rows instance: per-row reflected offset tables, compile-time 7x7 x 4
-#endif
-#ifndef DCS_TAG3
-#define DCS_TAG3 1  // PatchGAN layers 1-3: rows / x6 weight-gradient instances with the IN + LeakyReLU gather fixed
-#endif
-#ifndef DCS_UWALK
-#define DCS_UWALK 1  // slice-major rows gathers: the (tap, slice) walk in uniform registers (no per-lane tap decode)
-#endif
-#ifndef DCS_X6_BM256
-#define DCS_X6_BM256 1  // bf16x6 residual rows: 256 x 128 tiles (512 threads)
-#endif
-
+constexpr int X6_BK = 16;                // bf16x6 rows: k-tile depth (3 LDS planes, 16-deep tiles keep 2 blocks/CU)
+constexpr int X6_SGB = 5;                // bf16x6 residual rows: VALU instructions scheduled after each MFMA (0 = compiler)
+constexpr int WGRAD_SGB = 5;             // bf16x6 weight gradient: VALU instructions scheduled after each MFMA
+constexpr int X6_SGB0 = 0;               // ... the same for the other bf16x6 rows kernels
+constexpr int WGRAD_REDUCE_UNROLL = 8;   // slabs summed per unrolled round of the weight-gradient reduction
+constexpr int X6_OCC = 2;                // bf16x6 rows: workgroups per CU the register budget is sized for
+constexpr int H3_NSUB = 2;               // f16x3 rows, 128-column tiles: 16-k sub-tiles per barrier (64-column tiles: 1)
 
 // ---------------------------------------------------------------------------------------
 // geometry helpers
@@ -606,7 +533,6 @@ __device__ __forceinline__ void mfma_ktile(const float4 (&af)[IM][4], const floa
 // constants; the padding mode (reflect forward, zero for the dgrad) stays a runtime value.
 template <int TAG>
 __device__ __forceinline__ dcs_conv_desc specialise(dcs_conv_desc d) {
-#ifndef DCS_NO_SPECIALISE
     if constexpr (TAG == 1) {  // the residual-block convs: no prologue / epilogue activation
         d.KH = 3; d.KW = 3; d.stride = 1; d.up = 1; d.parity = 0;
         d.Cs = 256; d.csplit = 256; d.s_c = 1;
@@ -627,7 +553,6 @@ __device__ __forceinline__ dcs_conv_desc specialise(dcs_conv_desc d) {
         d.pro_act = DCS_ACT_LRELU; d.epi_act = DCS_ACT_NONE;
         d.pad_mode = DCS_PAD_ZERO; d.up = 1;
     }
-#endif
     return d;
 }
 
@@ -718,7 +643,7 @@ __device__ __forceinline__ void rows_in_stats(const dcs_conv_desc& d, const floa
 //      2 = four float4 taps per thread over a 4-channel NHWC source (Cs == 4, the stem)
 // BM = 256 (bf16x6, 128 columns): 512 threads as 4 x 2 waves of 64 x 64, one workgroup per CU;
 // every staged weight k-tile then feeds twice the pixels (0.75 of the 128-row tile's bytes per MFMA)
-// bf16x6 rows k-loop body: the fragment reads first, then each MFMA followed by DCS_X6_SGB
+// bf16x6 rows k-loop body: the fragment reads first, then each MFMA followed by X6_SGB
 // VALU instructions (the next tile's split and address arithmetic), then the LDS stores, so the
 // split runs in the shadow of the wave's own MFMAs instead of after them (0 = compiler order)
 template <int NMFMA, int NV, int NDSR = 12, int NDSW = 6>
@@ -735,7 +660,7 @@ __device__ __forceinline__ void x6_interleave() {
 }
 
 template <int BM, int BN, int VEC, int TAG, int MMA = MMA_F32>
-__global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || MMA == MMA_F16) ? (BM == 256 ? 2 : DCS_X6_OCC) : 2) void conv_rows_kernel(
+__global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || MMA == MMA_F16) ? (BM == 256 ? 2 : X6_OCC) : 2) void conv_rows_kernel(
     const dcs_conv_desc din, const float* __restrict__ src, const float* __restrict__ src2,
     const float* __restrict__ wp, const float* __restrict__ bias, const float* __restrict__ psc,
     const float* __restrict__ psh, float* __restrict__ out_, int gx, int gy, Part* __restrict__ parts, int fold_) {
@@ -756,8 +681,8 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
     // (32 k: the MFMAs per barrier of the 16-k bf16x6 tile), the 4-channel stem one
     constexpr bool H3 = MMA == MMA_F16X3 || MMA == MMA_F16;
     constexpr bool F1 = MMA == MMA_F16;  // f16: hi planes only, one product
-    constexpr int NSUB = (H3 && VEC == 1 && BN == 128) ? DCS_H3_NSUB : 1;  // 16-k sub-tiles per k-tile (split-at-store modes)
-    constexpr int BKT = MMA == MMA_BF16X6 ? DCS_X6_BK : (MMA == MMA_BF16P ? 48 : (H3 ? 16 * NSUB : BK));  // x6: 3 LDS planes, 16-deep tiles keep 2 blocks/CU
+    constexpr int NSUB = (H3 && VEC == 1 && BN == 128) ? H3_NSUB : 1;  // 16-k sub-tiles per k-tile (split-at-store modes)
+    constexpr int BKT = MMA == MMA_BF16X6 ? X6_BK : (MMA == MMA_BF16P ? 48 : (H3 ? 16 * NSUB : BK));  // x6: 3 LDS planes, 16-deep tiles keep 2 blocks/CU
     constexpr bool X6L = MMA == MMA_BF16X6 || MMA == MMA_BF16P || H3;  // the x6 LDS planes and pipeline
     constexpr bool X6F = MMA == MMA_BF16X6 || H3;  // operands split at the LDS store (prologue deferred there)
     constexpr int NSLOT = H3 ? 2 * NSUB : 3;       // LDS planes per buffer: [plane][sub] (H3), else 3
@@ -906,7 +831,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
     // L1/L2 instead of after a sweep over all channels (the dispatch requires d.korder == SLICE)
     // TAG 0 bf16x6 kernels with 16-channel-aligned sources walk the same slice-major order over
     // tap-major packed weights (KSB: the B column is rebuilt from (tap, channel) per k-tile)
-    constexpr bool KSB = TAG != 1 && X6F && VEC == 1 && DCS_KSLICE_ALL;
+    constexpr bool KSB = TAG != 1 && X6F && VEC == 1;
     constexpr bool KS = TAG == 1 || KSB;
     int aj, ac;
     if constexpr (KS) {
@@ -1000,7 +925,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
         adx = wox + wsx * w.tx;
         bt = wb0 + wbty * w.ty + wbtx * w.tx;
     };
-    constexpr bool UWALK = KS && DCS_UWALK;
+    constexpr bool UWALK = KS;
     Walk wa = walk_init(kb0 >> 4), wb = wa;
     const int alo = akq & 15, blo = bkq & 15;
     // linear gather (zero padding, no upsampling): the lane's element offset of tap (0, 0) at channel
@@ -1105,13 +1030,13 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
                 if constexpr (UWALK) walk_step(wa);
                 else advance16(aj, ac);
             }
-        } else if (VEC && MMA != MMA_F32 && DCS_BF16_BUFGATHER) {
+        } else if (VEC && MMA != MMA_F32) {
             // bf16 modes: branch-free gather through a buffer descriptor (OOB -> zeros)
             int sy = 0, sx = 0, off = OOB_OFF;
             // past the last k-tile (the x6 pipeline's unconditional prefetch) the walk leaves the
             // range through aj (tap-major) or through ac (slice-major): both must stay in range
             int c = ac;
-            if constexpr (UWALK && X6F && DCS_X6_SELGATHER && BKT == 16) {
+            if constexpr (UWALK && X6F && BKT == 16) {
                 const bool kin = wa.cs < d.Cs;
                 int ady, adx, bt;
                 walk_tap(wa, ady, adx, bt);
@@ -1126,7 +1051,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
                     off = (kin && rvalid && yok && xok) ? (ri.n * (int)d.s_n + sy * (int)d.s_h + sx * (int)d.s_w + c) * 4
                                                         : OOB_OFF;
                 }
-            } else if constexpr (X6F && DCS_X6_SELGATHER) {
+            } else if constexpr (X6F) {
                 // select form (tap 0 stands in for a tap past the end): no exec-mask branch
                 // splits the k-loop body, so the scheduler can spread the next tile's split
                 // arithmetic over this tile's MFMAs
@@ -1152,7 +1077,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
 #pragma unroll
                 for (int i = 0; i < ACH; ++i) dst[i] = affine_act4(dst[i], psc + so + ac + 4 * i, psh + so + ac + 4 * i, d.pro_act);
             }
-            if constexpr (UWALK && X6F && DCS_X6_SELGATHER && BKT == 16) {
+            if constexpr (UWALK && X6F && BKT == 16) {
                 walk_step(wa);
             } else {
                 advance(aj, ac);
@@ -1220,13 +1145,13 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
             for (int sub = 0; sub < NSUB; ++sub) {
                 long long col;
                 bool ok = true;
-                if constexpr (TAG == 1 && H3 && DCS_UWALK) {  // the (masked) slice-major walk: 9 taps x 16 per slice
+                if constexpr (TAG == 1 && H3) {  // the (masked) slice-major walk: 9 taps x 16 per slice
                     ok = wb.cs < d.Cs;
                     col = (long long)(wb.cs >> 4) * (9 * 16) + (wb.ty * 3 + wb.tx) * 16 + blo;
                     walk_step(wb);
                 } else if (!d.parity && !KSB) {
                     col = (long long)kt * BKT + 16 * sub + bkq;
-                } else if constexpr (KSB && DCS_UWALK) {
+                } else if constexpr (KSB) {
                     ok = wb.cs < d.Cs;
                     int ady, adx, bt;
                     walk_tap(wb, ady, adx, bt);
@@ -1265,7 +1190,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
         bool ok = true;
         if (!d.parity && !KSB) {
             col = kt * BKT + bkq;
-        } else if constexpr (KSB && DCS_UWALK && X6F && DCS_BF16_BUFGATHER && BKT == 16) {
+        } else if constexpr (KSB && X6F && BKT == 16) {
             ok = wb.cs < d.Cs;
             int ady, adx, bt;
             walk_tap(wb, ady, adx, bt);
@@ -1286,7 +1211,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
             dst[0] = make_float4(h.x, h.y, l.x, l.y);
             return;
         }
-        if constexpr (X6F && DCS_BF16_BUFGATHER) {  // branch-free: k-tiles past the end read zeros
+        if constexpr (X6F) {  // branch-free: k-tiles past the end read zeros
             const int off = (ok && col < d.ldb) ? (int)(((long long)(n0 + brow) * d.ldb + col) * 4) : OOB_OFF;
 #pragma unroll
             for (int i = 0; i < BCH; ++i) dst[i] = buf_load4(brsrc, off + 16 * i);
@@ -1541,7 +1466,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
                     }
             }
         };
-        if constexpr (X6L && DCS_X6_PIPE) {
+        if constexpr (X6L) {
             // two register sets: tile kt+2's gather is in flight while tile kt computes, so
             // staging tile kt+1 waits only for loads issued a whole k-tile earlier
             // The loads are issued unconditionally (k-tiles past the end gather zeros from the
@@ -1555,31 +1480,21 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
                 load_a(kt + 2, ra2, pa2);
                 load_b(kt + 2, rb2);
                 step(0, 0);
-                if (DCS_X6_STORE_FIRST) {
-                    // staging before the chain fold and unconditional (a tile past the end is
-                    // zeros into a buffer nobody reads again): one basic block with the MFMAs
-                    store_tiles(1, ra, rb, pa1);
-                    x6_interleave<IM * JN * (MMA == MMA_BF16P ? 3 : (H3 ? (F1 ? 1 : 3) * NSUB : 6)), (TAG == 1 && X6F) ? DCS_X6_SGB : DCS_X6_SGB0,
-                                  H3 ? (IM + JN) * (F1 ? 1 : 2) * NSUB : 12, H3 ? (F1 ? 2 : 4) * NSUB : 6>();
-                    fold_t(kt);
-                } else {
-                    fold_t(kt);
-                    if (kt + 1 < nkt) store_tiles(1, ra, rb, pa1);
-                }
+                // staging before the chain fold and unconditional (a tile past the end is
+                // zeros into a buffer nobody reads again): one basic block with the MFMAs
+                store_tiles(1, ra, rb, pa1);
+                x6_interleave<IM * JN * (MMA == MMA_BF16P ? 3 : (H3 ? (F1 ? 1 : 3) * NSUB : 6)), (TAG == 1 && X6F) ? X6_SGB : X6_SGB0,
+                              H3 ? (IM + JN) * (F1 ? 1 : 2) * NSUB : 12, H3 ? (F1 ? 2 : 4) * NSUB : 6>();
+                fold_t(kt);
                 __syncthreads();
                 if (kt + 1 >= nkt) break;
                 load_a(kt + 3, ra, pa1);
                 load_b(kt + 3, rb);
                 step(1, 0);
-                if (DCS_X6_STORE_FIRST) {
-                    store_tiles(0, ra2, rb2, pa2);
-                    x6_interleave<IM * JN * (MMA == MMA_BF16P ? 3 : (H3 ? (F1 ? 1 : 3) * NSUB : 6)), (TAG == 1 && X6F) ? DCS_X6_SGB : DCS_X6_SGB0,
-                                  H3 ? (IM + JN) * (F1 ? 1 : 2) * NSUB : 12, H3 ? (F1 ? 2 : 4) * NSUB : 6>();
-                    fold_t(kt + 1);
-                } else {
-                    fold_t(kt + 1);
-                    if (kt + 2 < nkt) store_tiles(0, ra2, rb2, pa2);
-                }
+                store_tiles(0, ra2, rb2, pa2);
+                x6_interleave<IM * JN * (MMA == MMA_BF16P ? 3 : (H3 ? (F1 ? 1 : 3) * NSUB : 6)), (TAG == 1 && X6F) ? X6_SGB : X6_SGB0,
+                              H3 ? (IM + JN) * (F1 ? 1 : 2) * NSUB : 12, H3 ? (F1 ? 2 : 4) * NSUB : 6>();
+                fold_t(kt + 1);
                 __syncthreads();
             }
         } else {
@@ -1937,7 +1852,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, int nsplit, in
     float s = 0.f;
     if (ci >= Cw) return;  // zero-padded source channel (no weight)
     // loads hoisted 8 at a time, the additions kept in split order (bit-identical sums)
-#pragma unroll DCS_WGRAD_REDUCE_UNROLL
+#pragma unroll WGRAD_REDUCE_UNROLL
     for (int q = 0; q < nsplit; ++q) s += ws[(long long)q * total + idx];
     dw[((long long)co * Cw + ci) * taps + tap] = s;
 }
@@ -2527,9 +2442,9 @@ int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2,
     if (d.korder != DCS_KORDER_TAP && d.korder != DCS_KORDER_SLICE) return fail(DCS_E_INVALID, "conv_rows: bad korder");
     hipStream_t s = as_stream(stream);
     const bool x6f = d.mma == MMA_BF16X6 || d.mma == MMA_F16X3 || d.mma == MMA_F16;  // split-at-store pipelines
-    const bool plain = DCS_TAG2 && d.pro_act == DCS_ACT_NONE && d.epi_act == DCS_ACT_NONE && d.pad_mode == DCS_PAD_ZERO &&
+    const bool plain = d.pro_act == DCS_ACT_NONE && d.epi_act == DCS_ACT_NONE && d.pad_mode == DCS_PAD_ZERO &&
                        d.up == 1;
-    const bool lrelu = DCS_TAG3 && d.pro_act == DCS_ACT_LRELU && d.epi_act == DCS_ACT_NONE && d.pad_mode == DCS_PAD_ZERO &&
+    const bool lrelu = d.pro_act == DCS_ACT_LRELU && d.epi_act == DCS_ACT_NONE && d.pad_mode == DCS_PAD_ZERO &&
                        d.up == 1;  // TAG 2 instances
 #define DCS_ROWS_X6F(BM_, BN_, VEC_, TAG_, G)                                                                          \
     if (d.mma == MMA_F16X3)                                                                                          \
@@ -2541,12 +2456,12 @@ int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2,
     else                                                                                                             \
         hipLaunchKernelGGL((conv_rows_kernel<BM_, BN_, VEC_, TAG_, MMA_BF16X6>), G, dim3(2 * BM_), 0, s, d, src, src2, \
                            wpack, bias, psc, psh, out, gxx, gy, parts, fold_arg);
-    if (vec && x6f && (BN == 128 || DCS_X6_BN64)) {  // x6 / f16x3: 128- or 64-column tiles
+    if (vec && x6f) {  // x6 / f16x3: 128- or 64-column tiles
         // 256-row tiles where they divide the pixels evenly (the forward over whole 128 x 128
         // images); the 130 x 130 padded data gradient keeps 128-row tiles (measured: its partial
         // last dispatch round and zero-padded border rows make the big tile 7 % slower there)
         int gxx = gx;
-        if (BN == 128 && res && DCS_X6_BM256 && Mmax % 256 == 0 && (!parts || ((long long)d.Ho * d.Wo) % 256 == 0)) {
+        if (BN == 128 && res && Mmax % 256 == 0 && (!parts || ((long long)d.Ho * d.Wo) % 256 == 0)) {
             gxx = (int)cdiv(Mmax, 256);
             const dim3 grid2((unsigned)(gxx * gy));
             DCS_ROWS_X6F(256, 128, 1, 1, grid2)
@@ -2560,9 +2475,9 @@ int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2,
         else { DCS_ROWS_X6F(128, 64, 1, 0, grid) }
         return check_launch("conv_rows");
     }
-    if (v4 && x6f && DCS_X6_V4) {  // 4-channel stem / PatchGAN layer 0
+    if (v4 && x6f) {  // 4-channel stem / PatchGAN layer 0
         const int gxx = gx;
-        const bool stem = DCS_TAG4 && d.KH == 7 && d.KW == 7 && d.Cs == 4 && d.stride == 1 && d.up == 1 && !d.parity &&
+        const bool stem = d.KH == 7 && d.KW == 7 && d.Cs == 4 && d.stride == 1 && d.up == 1 && !d.parity &&
                           d.pad_mode == DCS_PAD_REFLECT && d.pro_act == DCS_ACT_NONE && d.epi_act == DCS_ACT_NONE;
         if (BN == 128 && plain) { DCS_ROWS_X6F(128, 128, 2, 2, grid) }
         else if (BN == 128) { DCS_ROWS_X6F(128, 128, 2, 0, grid) }
@@ -2572,10 +2487,10 @@ int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2,
         return check_launch("conv_rows");
     }
 #undef DCS_ROWS_X6F
-    if (vec && d.mma == MMA_BF16 && res && BN == 128 && DCS_BF16P && DCS_BF16P_ROWS && d.ldb % 48 == 0) {
+    if (vec && d.mma == MMA_BF16 && res && BN == 128 && d.ldb % 48 == 0) {
         // residual convs in the half-precision mode: the x6 pipeline, 48 k per barrier; 256-row
         // tiles where they divide the pixels (the forward)
-        if (DCS_BF16P_BM256 && Mmax % 256 == 0 && (!parts || ((long long)d.Ho * d.Wo) % 256 == 0)) {
+        if (Mmax % 256 == 0 && (!parts || ((long long)d.Ho * d.Wo) % 256 == 0)) {
             const int gx2 = (int)cdiv(Mmax, 256);
             hipLaunchKernelGGL((conv_rows_kernel<256, 128, 1, 1, MMA_BF16P>), dim3((unsigned)(gx2 * gy)), dim3(512), 0, s,
                                d, src, src2, wpack, bias, psc, psh, out, gx2, gy, parts, fold_arg);
@@ -2929,15 +2844,13 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_x6_kernel(
                     }
             }
             store(cur ^ 1, ora, orb, opro);
-            if constexpr (DCS_WGRAD_SGB > 0) {
-                __builtin_amdgcn_sched_group_barrier(0x100, 2 * (IM + JN) * (F1 ? 1 : 2) * NSUB, 0);  // DS read
+            __builtin_amdgcn_sched_group_barrier(0x100, 2 * (IM + JN) * (F1 ? 1 : 2) * NSUB, 0);  // DS read
 #pragma unroll
-                for (int i = 0; i < IM * JN * (F1 ? 1 : 3) * NSUB; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, DCS_WGRAD_SGB, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x200, (F1 ? 2 : 4) * NSUB, 0);  // DS write
+            for (int i = 0; i < IM * JN * (F1 ? 1 : 3) * NSUB; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, WGRAD_SGB, 0);
             }
+            __builtin_amdgcn_sched_group_barrier(0x200, (F1 ? 2 : 4) * NSUB, 0);  // DS write
             const long long rel = kt - kt_beg;
             if ((rel % KT2) == KT2 - 1 || kt + 1 == kt_end) {
 #pragma unroll
@@ -3002,15 +2915,13 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_x6_kernel(
         // stage tile kt+1 before the chain fold, unconditionally (past the range: a buffer nobody
         // reads again), with the split spread over this tile's MFMAs
         store(cur ^ 1, ora, orb, opro);
-        if constexpr (DCS_WGRAD_SGB > 0) {
-            __builtin_amdgcn_sched_group_barrier(0x100, 24, 0);  // DS read (transposed fragments)
+        __builtin_amdgcn_sched_group_barrier(0x100, 24, 0);  // DS read (transposed fragments)
 #pragma unroll
-            for (int i = 0; i < IM * JN * 6; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, DCS_WGRAD_SGB, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x200, 6, 0);  // DS write
+        for (int i = 0; i < IM * JN * 6; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, WGRAD_SGB, 0);
         }
+        __builtin_amdgcn_sched_group_barrier(0x200, 6, 0);  // DS write
         const long long rel = kt - kt_beg;
         if ((rel % KT2) == KT2 - 1 || kt + 1 == kt_end) {
 #pragma unroll
@@ -3102,18 +3013,10 @@ WgradPlan wgrad_plan(const dcs_conv_desc& d) {
 
 // conv_win.hip: the f16x3 window weight gradient of the residual 3x3 convs
 namespace dcs {
-#ifndef DCS_X6_F16_TAG3  // the f16 PatchGAN weight gradients on the LeakyReLU-prologue instance (TAG 3) as in f16x3,
-                         // not the generic one: bit-identical, f16 step 128.26 -> 127.73 ms (profiles/r06/ab/r06aq_*)
-#define DCS_X6_F16_TAG3 1
-#endif
 bool wgrad_win_check(const dcs_conv_desc& d);
 size_t wgrad_win_workspace_size(const dcs_conv_desc& d);
 int wgrad_win_launch(const dcs_conv_desc& d, const float* dy, const float* x, float* ws, hipStream_t s);
-// conv_subpix.hip: the f16x3 window weight gradients of the up- and stride-2 convolutions (a VARIANT build
-// with EXTRA=-DDCS_SUBPIX_WGRAD=0 runs the x6 kernels instead, for A/B)
-#ifndef DCS_SUBPIX_WGRAD
-#define DCS_SUBPIX_WGRAD 1
-#endif
+// conv_subpix.hip: the f16x3 window weight gradient of the up-convolutions
 bool subpix_wgrad_check(const dcs_conv_desc& d);
 size_t subpix_wgrad_workspace_size(const dcs_conv_desc& d);
 int subpix_wgrad_launch(const dcs_conv_desc& d, const float* dy, const float* x, float* ws, hipStream_t s);
@@ -3128,15 +3031,15 @@ extern "C" size_t dcs_conv_wgrad_workspace_size(const dcs_conv_desc* dp) {
     if (!dp) return 0;
     WgradPlan p = wgrad_plan(*dp);
     size_t n = (size_t)p.nsplit * (dp->parity == 2 ? 4 : 1) * dp->Co * p.Ktot * sizeof(float);
-    if (DCS_WGRAD_WIN && wgrad_win_check(*dp)) {
+    if (wgrad_win_check(*dp)) {
         const size_t nw = wgrad_win_workspace_size(*dp);
         n = nw > n ? nw : n;
     }
-    if (DCS_SUBPIX_WGRAD && subpix_wgrad_check(*dp)) {
+    if (subpix_wgrad_check(*dp)) {
         const size_t nw = subpix_wgrad_workspace_size(*dp);
         n = nw > n ? nw : n;
     }
-    if (DCS_SUBPIX_WGRAD && s2_wgrad_check(*dp)) {
+    if (s2_wgrad_check(*dp)) {
         const size_t nw = s2_wgrad_workspace_size(*dp);
         n = nw > n ? nw : n;
     }
@@ -3161,7 +3064,7 @@ extern "C" int dcs_conv_wgrad(const dcs_conv_desc* dp, const float* dy, const fl
     if (d.parity == 2 && !vec) return fail(DCS_E_INVALID, "conv_wgrad: sub-pixel rows need a vectorisable source");
     hipStream_t s = as_stream(stream);
     float* w = reinterpret_cast<float*>(ws);
-    if (DCS_WGRAD_WIN && wgrad_win_check(d)) {  // f16x3 residual geometry: the rolling-window kernel
+    if (wgrad_win_check(d)) {  // f16x3 residual geometry: the rolling-window kernel
         const int ns = wgrad_win_launch(d, dy, x, w, s);
         if (ns < 0) return -ns;
         const long long total = (long long)d.Co * 9 * d.Cs;
@@ -3169,7 +3072,7 @@ extern "C" int dcs_conv_wgrad(const dcs_conv_desc* dp, const float* dy, const fl
                            3, 3, d.Cs, dw);
         return check_launch("conv_wgrad_reduce");
     }
-    if (DCS_SUBPIX_WGRAD && subpix_wgrad_check(d) && !x2) {  // f16x3 up-convolution: the rolling-window phase kernel
+    if (subpix_wgrad_check(d) && !x2) {  // f16x3 up-convolution: the rolling-window phase kernel
         const int ns = subpix_wgrad_launch(d, dy, x, w, s);
         if (ns < 0) return -ns;
         const long long tot9 = (long long)d.Co * d.Cs * 9;
@@ -3177,7 +3080,7 @@ extern "C" int dcs_conv_wgrad(const dcs_conv_desc* dp, const float* dy, const fl
                            d.Cs, dw);
         return check_launch("wgrad_subpixel_fold");
     }
-    if (DCS_SUBPIX_WGRAD && s2_wgrad_check(d) && !x2) {  // f16x3 stride-2 conv: the rolling class-window kernel
+    if (s2_wgrad_check(d) && !x2) {  // f16x3 stride-2 conv: the rolling class-window kernel
         const int ns = s2_wgrad_launch(d, dy, x, psc, psh, w, s);
         if (ns < 0) return -ns;
         const long long total = (long long)d.Co * d.KH * d.KW * d.Cs;
@@ -3191,10 +3094,10 @@ extern "C" int dcs_conv_wgrad(const dcs_conv_desc* dp, const float* dy, const fl
     const bool dy_small = (long long)d.N * d.Ho * d.Wo * d.Co * 4 < (long long)OOB_OFF - 64;
     // (the bf16 and bf16x3 modes run the bf16x6 weight gradient: a bf16 MFMA weight gradient measured
     // slower than the exact f32 one at every layer, its 8-pixel walk per thread VALU bound)
-    if (DCS_WGRAD_X6_V4 && (d.mma == MMA_F16X3 || d.mma == MMA_F16) && v4 && d.Cs == 4 && !d.parity && dy_small &&
+    if ((d.mma == MMA_F16X3 || d.mma == MMA_F16) && v4 && d.Cs == 4 && !d.parity && dy_small &&
                d.pro_act == DCS_ACT_NONE && (p.BM == 128 || d.Co == 64) && class_geom(d, 0).Mx >= 16) {
         // 4-channel sources (stem, PatchGAN layer 0) on the fp16 x6 pipeline: two taps per thread's 8 columns
-        const bool plain = DCS_TAG2 && d.pad_mode == DCS_PAD_ZERO && d.up == 1;
+        const bool plain = d.pad_mode == DCS_PAD_ZERO && d.up == 1;
         if (d.mma == MMA_F16X3) {
             if (plain) hipLaunchKernelGGL((conv_wgrad_x6_kernel<2, MMA_F16X3, true>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
             else hipLaunchKernelGGL((conv_wgrad_x6_kernel<0, MMA_F16X3, true>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
@@ -3202,12 +3105,12 @@ extern "C" int dcs_conv_wgrad(const dcs_conv_desc* dp, const float* dy, const fl
             if (plain) hipLaunchKernelGGL((conv_wgrad_x6_kernel<2, MMA_F16, true>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
             else hipLaunchKernelGGL((conv_wgrad_x6_kernel<0, MMA_F16, true>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
         }
-    } else if (d.mma != MMA_F32 && vec && dy_small && (p.BM == 128 || (d.Co == 64 && DCS_WGRAD_X6_CO64 && (d.mma == MMA_F16X3 || d.mma == MMA_F16))) &&
-               d.parity != 1 && class_geom(d, 0).Mx >= 16 && DCS_WGRAD_X6) {  // one row wrap per tile
+    } else if (d.mma != MMA_F32 && vec && dy_small && (p.BM == 128 || (d.Co == 64 && (d.mma == MMA_F16X3 || d.mma == MMA_F16))) &&
+               d.parity != 1 && class_geom(d, 0).Mx >= 16) {  // one row wrap per tile
         // 16-pixel tiles: twice the tile count per split, the same pixel ranges and slabs.  (The
         // 64-output-channel layers could run the 128-row tile half masked: slower than f32.)
-        const bool plain = DCS_TAG2 && d.pro_act == DCS_ACT_NONE && d.pad_mode == DCS_PAD_ZERO && d.up == 1;
-        const bool lrelu = DCS_TAG3 && d.pro_act == DCS_ACT_LRELU && d.pad_mode == DCS_PAD_ZERO && d.up == 1;
+        const bool plain = d.pro_act == DCS_ACT_NONE && d.pad_mode == DCS_PAD_ZERO && d.up == 1;
+        const bool lrelu = d.pro_act == DCS_ACT_LRELU && d.pad_mode == DCS_PAD_ZERO && d.up == 1;
         if (d.mma == MMA_F16X3) {  // f16x3: two 16-pixel sub-tiles per barrier
             if (res) hipLaunchKernelGGL((conv_wgrad_x6_kernel<1, MMA_F16X3>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
             else if (plain) hipLaunchKernelGGL((conv_wgrad_x6_kernel<2, MMA_F16X3>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
@@ -3216,9 +3119,9 @@ extern "C" int dcs_conv_wgrad(const dcs_conv_desc* dp, const float* dy, const fl
         } else if (d.mma == MMA_F16) {  // f16: the same pipeline, one product
             if (res) hipLaunchKernelGGL((conv_wgrad_x6_kernel<1, MMA_F16>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
             else if (plain) hipLaunchKernelGGL((conv_wgrad_x6_kernel<2, MMA_F16>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
-            else if (lrelu && DCS_X6_F16_TAG3) hipLaunchKernelGGL((conv_wgrad_x6_kernel<3, MMA_F16>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
+            else if (lrelu) hipLaunchKernelGGL((conv_wgrad_x6_kernel<3, MMA_F16>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
             else hipLaunchKernelGGL((conv_wgrad_x6_kernel<0, MMA_F16>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
-        } else if (d.mma == MMA_BF16 && DCS_BF16P) {  // half precision: one product, 48 pixels per barrier
+        } else if (d.mma == MMA_BF16) {  // half precision: one product, 48 pixels per barrier
             if (res) hipLaunchKernelGGL((conv_wgrad_x6_kernel<1, MMA_BF16P>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
             else hipLaunchKernelGGL((conv_wgrad_x6_kernel<0, MMA_BF16P>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);
         } else if (res) hipLaunchKernelGGL((conv_wgrad_x6_kernel<1>), grid, dim3(NT), 0, s, d, dy, x, psc, psh, w, 2 * p.kt_per_split, gn, gm);

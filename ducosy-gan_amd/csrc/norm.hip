@@ -4,12 +4,7 @@
 // then a fixed-order merge) and therefore deterministic.
 #include "common.hpp"
 
-#ifndef DCS_NORM_BATCH
-#define DCS_NORM_BATCH 1  // IN apply / backward apply: whole-block fast path with every load issued first
-#endif
-#ifndef DCS_NORM_PUNROLL
-#define DCS_NORM_PUNROLL 1  // IN backward partial sums: pixel-loop unroll (4 measured 1.5 % slower)
-#endif
+constexpr int NORM_PUNROLL = 1;  // IN backward partial sums: pixel-loop unroll (4 measured 1.5 % slower)
 
 namespace dcs {
 
@@ -267,7 +262,7 @@ __global__ __launch_bounds__(256) void in_apply_pow2_kernel(const float4* __rest
     float4* os = out + (long long)n * per_n4;
     const int i0 = blockIdx.x * 1024 + threadIdx.x;
     float m = 0.f;
-    if (DCS_NORM_BATCH && i0 + 768 < per_n4) {  // whole block in range: the 4 loads issued together
+    if (i0 + 768 < per_n4) {  // whole block in range: the 4 loads issued together (fast path)
         float4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = xs[i0 + 256 * u];
@@ -363,7 +358,7 @@ __global__ __launch_bounds__(256) void in_bwd_partial_v4_kernel(const float4* __
     const float s[4] = {s4.x, s4.y, s4.z, s4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
     const long long base = (long long)n * HW * cq + c4;
     float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll DCS_NORM_PUNROLL
+#pragma unroll NORM_PUNROLL
     for (int p = p0 + plane; p < p1; p += lanes) {
         const float4 g4 = da[base + (long long)p * cq], y4 = y[base + (long long)p * cq];
         const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, yv[4] = {y4.x, y4.y, y4.z, y4.w};
@@ -418,7 +413,7 @@ __global__ __launch_bounds__(256) void in_bwd_apply_pow2_kernel(const float4* __
     const long long off = (long long)n * per_n4;
     const int i0 = blockIdx.x * 1024 + threadIdx.x;
     float m = 0.f;
-    if (DCS_NORM_BATCH && i0 + 768 < per_n4) {  // whole block in range: the 8 loads issued together
+    if (i0 + 768 < per_n4) {  // whole block in range: the 8 loads issued together (fast path)
         float4 g4u[4], y4u[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {

@@ -1,3 +1,4 @@
+# Archive: needs a -DCLK_PROBE=1 build of commit 35c0232 or earlier (the probe regions were removed from csrc/conv_win.hip afterwards).
 # core clock of the residual weight gradient in the bench step and the bench value for probe
 # libraries:  bash scripts/r05/clk_ab.sh TAG VARIANT...   (each VARIANT a -DCLK_PROBE=1 build)
 set -o pipefail

@@ -1,3 +1,4 @@
+# Archive: needs a -DCLK_PROBE=1 build of commit 35c0232 or earlier (the probe regions were removed from csrc/conv_win.hip afterwards).
 """Core clock during the residual weight-gradient kernel of the bench step (probe library built with
 -DCLK_PROBE=1): runs bench.py's step, then reads the last launch's per-workgroup core-cycle and
 wall-clock (100 MHz) counters.   DUCOSY_HIP_LIB=... python scripts/r05/clk_probe.py [bench args]"""

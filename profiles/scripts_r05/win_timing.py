@@ -1,3 +1,4 @@
+# Archive: needs a -DWIN_TIMING=1 build of commit 35c0232 or earlier (the probe regions were removed from csrc/conv_win.hip afterwards).
 """Per-workgroup phase times of the residual window conv forward (probe library built with
 -DWIN_TIMING=1: DUCOSY_HIP_LIB=.../libducosy_hip_tm.so): prologue (start -> first barrier), k loop,
 epilogue (stores retired), and the gap between a CU's consecutive workgroups.

@@ -38,7 +38,7 @@ def _geom(ops, cin=256, cout=256):
     return ops.ConvGeom(cin, cout, 3, 1, (1, 1, 1, 1), DCS_PAD_REFLECT)
 
 
-@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 32, 32), (2, 16, 64), (1, 8, 128)])
+@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 32, 32), (2, 16, 64), (1, 8, 128), (2, 32, 8)])
 def test_win_forward_and_stats_vs_fp64(ops, N, H, W):
     ops.set_mma("f16x3")
     g = _geom(ops)
@@ -66,7 +66,7 @@ def test_win_forward_and_stats_vs_fp64(ops, N, H, W):
 
 
 @pytest.mark.parametrize("addend", [False, True])
-@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 16, 128), (5, 32, 32), (3, 16, 64), (2, 8, 128)])
+@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 16, 128), (5, 32, 32), (3, 16, 64), (2, 8, 128), (2, 32, 8)])
 def test_win_dgrad_reflect_vs_fp64(ops, N, H, W, addend):
     """The reflect-pad data gradient: interior by the window kernel, the padded grid's ring by
     ring16_kernel (ring segments over the batch in 64-position tiles: the sizes here leave partial
@@ -150,7 +150,7 @@ def test_win_wgrad_vs_fp64(ops, N, H, W):
     assert e_win <= 1.5 * e_f32 + 1e-7, (e_win, e_f32)
 
 
-@pytest.mark.parametrize("N,H,W", [(2, 16, 64), (1, 16, 128)])
+@pytest.mark.parametrize("N,H,W", [(2, 16, 64), (1, 16, 128), (2, 32, 8)])
 def test_win_f16_mode_vs_fp64(ops, N, H, W):
     """BASELINE config 5's fp16 MFMA path (DCS_MMA_F16: the window kernels with the hi planes only,
     one product): forward, data gradient and weight gradient within 3e-3 of float64 (fp16 operands:
@@ -176,9 +176,9 @@ def test_win_f16_mode_vs_fp64(ops, N, H, W):
 
 @pytest.mark.parametrize("N,H,W", [(1, 18, 64), (2, 16, 64), (1, 20, 128), (1, 9, 64)])
 def test_win_wgrad_f16_vs_fp64(ops, N, H, W):
-    """The f16 mode's weight gradient (wgrad3_win16_kernel<1>: two image rows per barrier, the next
-    two staged through the second) over row chunks with an odd row count (H 18: two chunks of 9, H 9:
-    one) and several strips: within 3e-3 of float64 and bit-identical on a second run."""
+    """The f16 mode's weight gradient (wgrad3_win_h3_kernel<1>: two image rows per barrier, each row's
+    successor in the ring loaded at its start and staged at its end) over row chunks with an odd
+    row count (H 18: two chunks of 9, H 9: one) and several strips: within 3e-3 of float64 and bit-identical on a second run."""
     g = _geom(ops)
     x = rnd((N, 256, H, W), 121, "x").double()
     w = torch.from_numpy(prng.normal(122, "w", (256, 256, 3, 3), 0, 0.05)).float().double().requires_grad_(True)
