@@ -21,8 +21,13 @@ Differences from the reference, all deliberate:
     (modules/metrics.py::ms_ssim_levels; torchmetrics is not installed, so parity with the
     reference's own numbers is unpinned); without the flag its column is empty.  It is defined
     for slices of at least 176 x 176 and is empty below that, as in the reference;
-  * LPIPS needs the lpips library and its AlexNet weights and is left empty, as the reference
-    leaves it without them; the box and scatter plots need seaborn and are skipped;
+  * LPIPS is computed only with --lpips_weights PATH[,PATH], on either --device: the lpips library
+    is not needed, the metric (lpips.LPIPS(net='alex')) is restated from the package's defaults
+    (modules/metrics.py::lpips_taps) on the weights in the named torch.save'd state dicts, either
+    lpips.LPIPS(net='alex').state_dict() or torchvision's alexnet plus the package's alex.pth
+    (modules/lpips_weights.py); parity with the reference's own numbers is unpinned.  Without the
+    flag its column is empty, as the reference leaves it without the library, and so it is for
+    slices below 31 x 31; the box and scatter plots need seaborn and are skipped;
   * nothing happens at import or while parsing arguments: no environment variable is set and no
     directory is created before the conversion starts.
 DICOM files are read with modules/dicom.py.
@@ -66,12 +71,17 @@ def get_args(argv=None):
     p.add_argument("--reset", action="store_true", help="Remove the calculation output directory first")
     p.add_argument("--mask", action="store_true", help="Calculate the metrics on the masked series")
     p.add_argument("--skip_convert", action="store_true", help="Reuse the .npy stacks of an earlier run")
-    p.add_argument("--use_gpu", action="store_true", help="Accepted for compatibility (LPIPS is not computed; see --device and --ms_ssim)")
+    p.add_argument("--use_gpu", action="store_true", help="Accepted for compatibility (the metrics, MS-SSIM and LPIPS run where --device says; see --ms_ssim "
+                        "and --lpips_weights)")
     p.add_argument("--num_workers", type=int, default=1, help="Accepted for compatibility (patients run in sequence)")
     p.add_argument("--device", choices=["cpu", "cuda"], default="cpu",
                    help="cuda: compute the metrics with the HIP kernels; cpu: numpy / scipy on the host")
     p.add_argument("--ms_ssim", action="store_true",
                    help="Compute MS-SSIM of STD against Generated (slices of at least 176 x 176), on either --device")
+    p.add_argument("--lpips_weights", type=str, default=None, metavar="PATH[,PATH]",
+                   help="Compute LPIPS (AlexNet) of STD against Generated (slices of at least 31 x 31), on either "
+                        "--device, with the weights in these torch.save'd state dicts: lpips.LPIPS(net='alex')'s, "
+                        "or torchvision's alexnet and the lpips package's alex.pth")
     return p.parse_args(argv)
 
 
@@ -147,7 +157,7 @@ def convert(args):
     return out_dir, data_dir, tasks
 
 
-def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=False):
+def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=False, lpips_weights=None):
     """Metrics of one patient and its detail CSV; None when the STD or generated stack is missing."""
     path = lambda c: os.path.join(data_dir, f"{dataset}_{patient}_{c}.npy")
     if not (os.path.exists(path("std")) and os.path.exists(path("generated"))):
@@ -156,10 +166,11 @@ def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=Fals
         std, gen = np.load(path("std")), np.load(path("generated"))
         vue = np.load(path("vue")) if os.path.exists(path("vue")) else None
         if device is None:
-            patient_metrics, csv_data = M.evaluate_patient(std, gen, vue, ms_ssim)
+            patient_metrics, csv_data = M.evaluate_patient(std, gen, vue, ms_ssim, lpips_weights)
         else:
             from modules import metrics_gpu
-            patient_metrics, csv_data = metrics_gpu.evaluate_patient(std, gen, vue, device=device, ms_ssim=ms_ssim)
+            patient_metrics, csv_data = metrics_gpu.evaluate_patient(std, gen, vue, device=device, ms_ssim=ms_ssim,
+                                                                    lpips_weights=lpips_weights)
         try:
             M.write_detail_csv(os.path.join(detail_dir, f"{dataset}_{patient}_metrics.csv"), csv_data, vue is not None)
         except Exception as e:
@@ -171,7 +182,7 @@ def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=Fals
         return None
 
 
-def calculate(out_dir, data_dir, tasks, device, ms_ssim=False):
+def calculate(out_dir, data_dir, tasks, device, ms_ssim=False, lpips_weights=None):
     print(f"\nCalculating metrics for generated images (device: {device or 'cpu'})...")
     result_path = os.path.join(out_dir, "result_all_metrics.pkl")
     detail_dir = os.path.join(out_dir, "detail")
@@ -187,7 +198,7 @@ def calculate(out_dir, data_dir, tasks, device, ms_ssim=False):
         summary = {k: [] for k in M.METRICS}
         valid = 0
         for n, (dataset, patient) in enumerate(tasks, 1):
-            res = process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim)
+            res = process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim, lpips_weights)
             print(f"  [{n}/{len(tasks)}] {dataset} {patient}: {'done' if res is not None else 'skipped'}")
             if res is None:
                 continue
@@ -250,9 +261,13 @@ def summary_statistics(detail_dir, summary_csv_path):
 def main(argv=None):
     args = get_args(argv)
     device = f"cuda:{args.gpu_id}" if args.device == "cuda" else None
+    lpips_weights = None
+    if args.lpips_weights:   # loaded once, before any work: a bad file fails here
+        from modules import lpips_weights as LW
+        lpips_weights = LW.load(args.lpips_weights)
     out_dir, data_dir, tasks = convert(args)
     if tasks:
-        calculate(out_dir, data_dir, tasks, device, args.ms_ssim)
+        calculate(out_dir, data_dir, tasks, device, args.ms_ssim, lpips_weights)
     else:
         print("No tasks found. Please check input directories and arguments.")
     summary_statistics(os.path.join(out_dir, "detail"),

@@ -1705,13 +1705,12 @@ __global__ __launch_bounds__(NT, 2) void conv_wgrad_kernel(
             const int off = ok ? (pn * (int)d.s_n + sy * (int)d.s_h + sx * (int)d.s_w + bchan) * 4 : OOB_OFF;
 #pragma unroll
             for (int i = 0; i < BCH; ++i) rb[i] = buf_load4(rsrc, off + 16 * i);
-            if (d.pro_act != DCS_ACT_NONE) {
+            // a masked row (!ok) keeps the zeros of its OOB_OFF loads and must not touch psc / psh: past the
+            // last pixel pn runs beyond N (by BK / (My * Mx) images on small maps), outside the [N][Cs] arrays
+            if (d.pro_act != DCS_ACT_NONE && ok) {
                 const long long o = (long long)pn * d.Cs + bchan;
 #pragma unroll
-                for (int i = 0; i < BCH; ++i) {
-                    const float4 v = affine_act4(rb[i], psc + o + 4 * i, psh + o + 4 * i, d.pro_act);
-                    rb[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
+                for (int i = 0; i < BCH; ++i) rb[i] = affine_act4(rb[i], psc + o + 4 * i, psh + o + 4 * i, d.pro_act);
             }
             advance_pix();
         } else if (p < P) {

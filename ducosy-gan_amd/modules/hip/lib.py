@@ -195,6 +195,9 @@ SIGNATURES = {
     "dcs_met_msssim_level": (c_int, [P, P, c_int, c_int, c_int, POINTER(c_double), c_double, c_double, P, P, c_size_t,
                                      P]),
     "dcs_met_pool2": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "dcs_lpips_stem": (c_int, [P, c_int, c_int, c_int, c_float, c_float, P, P, P, P]),
+    "dcs_lpips_tap_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "dcs_lpips_tap": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     "dcs_unet_normalize_hu": (c_int, [P, c_int64, c_int, P, P]),
     "dcs_unet_affine_relu_pool": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, P]),
     "dcs_unet_upsample2_pad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),

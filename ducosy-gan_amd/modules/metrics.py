@@ -17,8 +17,9 @@ on numpy's float32 pairwise sums, so the arithmetic is fixed here, and modules/m
 ms_ssim restates torchmetrics' MultiScaleStructuralSimilarityIndexMeasure(data_range=1.0) with
 its defaults (rules at ``ms_ssim_levels``).  torchmetrics is not installed, so parity with the
 reference's own output is unpinned; the two paths here agree with each other and with a direct
-float64 formula (tests/test_cpu_msssim.py, tests/test_gpu_msssim.py).  lpips needs the lpips
-library and returns ``(nan, [])`` as the reference does without it.
+float64 formula (tests/test_cpu_msssim.py, tests/test_gpu_msssim.py).  lpips restates
+lpips.LPIPS(net='alex') with ATen on weights the user names (modules/lpips_weights.py; rules at
+``lpips_taps``) and returns ``(nan, [])`` without them, as the reference does without the library.
 """
 from __future__ import annotations
 
@@ -40,6 +41,7 @@ MS_SSIM_BETAS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 MS_SSIM_TAPS = 11
 MS_SSIM_MIN_SIDE = 176   # the fifth level must hold one window: 176 -> 88 -> 44 -> 22 -> 11
 MS_SSIM_C1, MS_SSIM_C2 = 0.01 ** 2, 0.03 ** 2
+LPIPS_MIN_SIDE = 31      # AlexNet's maps: 31 -> 7 -> 3 -> 3 -> 1; at 30 the second pool has no output
 _g = np.exp(-((np.arange(MS_SSIM_TAPS, dtype=np.float64) - 5) / 1.5) ** 2 / 2)
 MS_SSIM_WINDOW = _g / _g.sum()
 MS_SSIM_WINDOW.setflags(write=False)
@@ -227,8 +229,98 @@ def ms_ssim(img1, img2) -> Result:
     return ms_ssim_result(vals) if vals else (float("nan"), [])
 
 
-def lpips(img1, img2) -> Result:
-    return float("nan"), []
+def lpips_defined(shape) -> bool:
+    return len(shape) == 3 and min(shape[1:]) >= LPIPS_MIN_SIDE
+
+
+def lpips_input(x) -> np.ndarray:
+    """The reference's input chain in float32: the re-normalised volume mapped to [-1, 1]."""
+    return ms_ssim_renormalize(x) * np.float32(2) - np.float32(1)
+
+
+def lpips_features(x, weights, dtype=None, stem=None):
+    """The five ReLU outputs of the AlexNet trunk for slices x [N,H,W] (values of lpips_input; an
+    array, or a tensor with the weights on its device), as torch tensors [N,C,h,w] of ``dtype``
+    (default float32).  ``stem``: a function (x [N,1,H,W],
+    weights) -> the first convolution's output before the ReLU, in place of the scaling layer on
+    three equal channels and the 3-channel convolution (tests/test_cpu_lpips.py: the folds)."""
+    import torch
+    import torch.nn.functional as F
+    from . import lpips_weights as LW
+    dtype = dtype or torch.float32
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+    x = x.to(dtype).unsqueeze(1)
+    feats = []
+    for k, (_, _, _, stride, pad, pool) in enumerate(LW.CONVS):
+        w, b = (t.to(dtype) for t in weights.convs[k])
+        if k == 0 and stem is not None:
+            x = stem(x, weights)
+        elif k == 0:
+            shift = torch.tensor(LW.SHIFT, dtype=dtype, device=x.device).view(1, 3, 1, 1)
+            scale = torch.tensor(LW.SCALE, dtype=dtype, device=x.device).view(1, 3, 1, 1)
+            x = F.conv2d((x.repeat(1, 3, 1, 1) - shift) / scale, w, b, stride=stride, padding=pad)
+        else:
+            x = F.conv2d(F.max_pool2d(x, 3, 2) if pool else x, w, b, stride=stride, padding=pad)
+        x = F.relu(x)
+        feats.append(x)
+    return feats
+
+
+def lpips_tap(f1, f2, lin):
+    """One tap's distance of two feature tensors [N,C,h,w] -> [N]: channel-wise unit normalisation
+    (eps 1e-10 on the norm), squared difference, the 1x1 projection ``lin`` [C], the spatial mean."""
+    n1 = f1 / (f1.pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
+    n2 = f2 / (f2.pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
+    return ((n1 - n2).pow(2) * lin.to(f1.dtype).view(1, -1, 1, 1)).sum(1).mean((1, 2))
+
+
+def lpips_taps(img1, img2, weights, dtype=None) -> np.ndarray:
+    """float64 [5][D]: per tap and slice the spatial mean of the ``lin``-weighted squared difference
+    of the unit-normalised features, computed with ATen on the host in ``dtype`` (default float32,
+    as the reference does on the CPU; float64 is the oracle of the tests).  The rules, lpips 0.1.4
+    with net='alex', version='0.1', lpips=True, spatial=False in eval mode restated:
+
+      * both volumes go through lpips_input in float32, then the scaling layer (x - shift) / scale
+        on three equal channels;
+      * torchvision's AlexNet ``features`` with zero padding, biases and floor-sized 3x3 stride-2
+        max pools; the five ReLU outputs are the taps (modules/lpips_weights.py::CONVS);
+      * per tap lpips_tap; a slice's value is the sum over the taps.
+    Slices are independent, so they run in chunks.  Raises ValueError below 31 pixels on a side."""
+    import torch
+    a, b = _pair(img1, img2)
+    if not lpips_defined(a.shape):
+        raise ValueError(f"lpips: both sides of a slice must be at least {LPIPS_MIN_SIDE}")
+    xa, xb = lpips_input(a), lpips_input(b)
+    step = max(1, (1 << 22) // (a.shape[1] * a.shape[2]))
+    out = np.empty((len(weights.lins), a.shape[0]), dtype=np.float64)
+    with torch.no_grad():
+        for i in range(0, a.shape[0], step):
+            fa = lpips_features(xa[i:i + step], weights, dtype)
+            fb = lpips_features(xb[i:i + step], weights, dtype)
+            for k, lin in enumerate(weights.lins):
+                out[k, i:i + step] = lpips_tap(fa[k], fb[k], lin).to(torch.float64).numpy()
+    return out
+
+
+def lpips_from_taps(taps) -> Result:
+    """The sum over the taps per slice, and the mean over the slices (shared with the device path)."""
+    vals = np.asarray(taps, dtype=np.float64).sum(axis=0)
+    return float(np.mean(vals)), vals.tolist()
+
+
+def lpips(img1, img2, weights=None, dtype=None) -> Result:
+    """lpips.LPIPS(net='alex') of the re-normalised volumes with the given weights
+    (modules/lpips_weights.py): the mean over the slices and the per-slice values.  ``(nan, [])``
+    without weights, as the reference gives without the library, and below 31 pixels on a side,
+    where the package refuses the image.  The rules are at lpips_taps; the weights come from
+    files, so parity with the reference's own output is unpinned."""
+    if weights is None:
+        return float("nan"), []
+    a, b = _pair(img1, img2)
+    if not lpips_defined(a.shape):
+        return float("nan"), []
+    return lpips_from_taps(lpips_taps(a, b, weights, dtype))
 
 
 _ms_ssim = ms_ssim   # evaluate_pair's switch carries the function's name
@@ -297,16 +389,17 @@ def ed(img1, img2) -> Result:
     return float(np.mean(vals)), vals
 
 
-def evaluate_pair(target, pred, advanced: bool = True, ms_ssim: bool = False) -> Dict[str, Result]:
+def evaluate_pair(target, pred, advanced: bool = True, ms_ssim: bool = False, lpips_weights=None) -> Dict[str, Result]:
     """The basic metrics on the raw and the normalised volumes, and the advanced ones if asked;
-    MS-SSIM is computed only with ``ms_ssim=True`` and is ``(nan, [])`` otherwise."""
+    MS-SSIM is computed only with ``ms_ssim=True`` and LPIPS only with ``lpips_weights`` (loaded by
+    modules/lpips_weights.py); each is ``(nan, [])`` otherwise."""
     ms = _ms_ssim if ms_ssim else lpips   # not asked for: empty, as lpips is
     t, p = _pair(target, pred)
     tn, pn = normalize(t), normalize(p)
     out = {"mae": mae(t, p), "psnr": psnr(t, p), "ssim": ssim(t, p),
            "mae_norm": mae(tn, pn), "psnr_norm": psnr(tn, pn), "ssim_norm": ssim(tn, pn)}
     if advanced:
-        out.update({"ms_ssim": ms(tn, pn), "lpips": lpips(tn, pn), "emd": emd(t, p), "ts": ts(t, p),
+        out.update({"ms_ssim": ms(tn, pn), "lpips": lpips(tn, pn, lpips_weights), "emd": emd(t, p), "ts": ts(t, p),
                     "cs": cs(t, p), "ed": ed(t, p)})
     return out
 
@@ -315,11 +408,11 @@ def pair_names(has_vue: bool) -> List[str]:
     return ["STD_vs_Generated"] + (["VUE_vs_STD", "VUE_vs_Generated"] if has_vue else [])
 
 
-def collect_patient(pair_fn, std, gen, vue=None, ms_ssim: bool = False):
+def collect_patient(pair_fn, std, gen, vue=None, ms_ssim: bool = False, lpips_weights=None):
     """The per-patient driver both paths share: the basic metrics for every pair, the advanced
     ones for STD against Generated; series are cut to the shortest.  ``pair_fn(target, pred,
     advanced)`` is evaluate_pair of the host or of the device module; with ``ms_ssim`` it is
-    called with ``ms_ssim=True`` as well.  Returns (patient_metrics,
+    called with ``ms_ssim=True`` as well, with ``lpips_weights`` with those.  Returns (patient_metrics,
     csv_data): per metric the list of aggregates and the list of per-slice lists, one per pair."""
     n = min(len(v) for v in (std, gen, vue) if v is not None)
     std, gen = std[:n], gen[:n]
@@ -330,6 +423,8 @@ def collect_patient(pair_fn, std, gen, vue=None, ms_ssim: bool = False):
     patient = {k: [] for k in METRICS}
     per_slice = {k: [] for k in METRICS}
     kw = {"ms_ssim": True} if ms_ssim else {}
+    if lpips_weights is not None:
+        kw["lpips_weights"] = lpips_weights
     for targ, pred, adv in pairs:
         for k, (agg, lst) in pair_fn(targ, pred, adv, **kw).items():
             patient[k].append(agg)
@@ -337,8 +432,8 @@ def collect_patient(pair_fn, std, gen, vue=None, ms_ssim: bool = False):
     return patient, per_slice
 
 
-def evaluate_patient(std, gen, vue=None, ms_ssim: bool = False):
-    return collect_patient(evaluate_pair, std, gen, vue, ms_ssim)
+def evaluate_patient(std, gen, vue=None, ms_ssim: bool = False, lpips_weights=None):
+    return collect_patient(evaluate_pair, std, gen, vue, ms_ssim, lpips_weights)
 
 
 def detail_header(has_vue: bool) -> List[str]:

@@ -16,7 +16,10 @@ docstring, so the two paths agree to the rounding of float64 sums taken in diffe
   * MS-SSIM, computed only when asked for, re-normalises both volumes, pools them four times
     (one launch per level for the pair) and takes one pass per level; the level means come to
     the host and the powers and the product run there, shared with the host path.  Parity with
-    torchmetrics is unpinned (modules/metrics.py).
+    torchmetrics is unpinned (modules/metrics.py);
+  * LPIPS, computed only with weights, runs the AlexNet trunk on both volumes in chunks of slices
+    (modules/hip/lpips.py): the first layer reads the normalised volumes and re-normalises on the
+    fly, and only the five per-slice tap sums come to the host.
 
 Only per-slice float64 vectors come back to the host.  No CPU fallback: host tensors raise.
 """
@@ -28,6 +31,7 @@ import numpy as np
 import torch
 
 from . import metrics as M
+from .hip import lpips as L
 from .hip import metrics as K
 
 Result = M.Result
@@ -182,7 +186,31 @@ def ms_ssim(img1, img2) -> Result:
     return M.ms_ssim_result(vals) if vals else (float("nan"), [])
 
 
-lpips = M.lpips
+def lpips_taps(img1, img2, weights, chunk: Optional[int] = None) -> np.ndarray:
+    """modules/metrics.py::lpips_taps on the device: float64 [5][D], the only values that come to
+    the host besides the extrema of the re-normalisation.  ``chunk``: slices per pass (default: as
+    many as keep the feature maps within modules/hip/lpips.py::CHUNK_BYTES); no value depends on it."""
+    a, b = K._pair(img1, img2, "lpips")
+    if not M.lpips_defined(a.shape):
+        raise ValueError(f"lpips: both sides of a slice must be at least {M.LPIPS_MIN_SIDE}")
+    st = PairStats(a, b)
+    # div = range + 1e-8f is never 0; the first layer's kernel re-normalises while it reads
+    aff = (float(st.amin), float(_rng32(st.amin, st.amax) + M.EPS32), float(st.bmin), float(_rng32(st.bmin, st.bmax) + M.EPS32))
+    sums = L.tap_sums(a, b, aff, weights, chunk).cpu().numpy()
+    counts = np.array([h * w for h, w in L.LW.out_sizes(a.shape[1], a.shape[2])], np.float64)
+    return sums / counts[:, None]
+
+
+def lpips(img1=None, img2=None, weights=None, chunk: Optional[int] = None) -> Result:
+    """modules/metrics.py::lpips on device tensors; ``(nan, [])`` without weights and below 31
+    pixels on a side, without a launch."""
+    if weights is None:
+        return float("nan"), []
+    if isinstance(img1, torch.Tensor) and img1.dim() == 3 and not M.lpips_defined(img1.shape):
+        return float("nan"), []
+    return M.lpips_from_taps(lpips_taps(img1, img2, weights, chunk))
+
+
 _ms_ssim = ms_ssim
 
 
@@ -193,7 +221,8 @@ def to_device(x, device) -> torch.Tensor:
     return x.to(device=device, dtype=torch.float32)
 
 
-def evaluate_pair(target, pred, device, advanced: bool = True, ms_ssim: bool = False) -> Dict[str, Result]:
+def evaluate_pair(target, pred, device, advanced: bool = True, ms_ssim: bool = False,
+                  lpips_weights=None) -> Dict[str, Result]:
     """modules/metrics.py::evaluate_pair on ``device``."""
     t, p = to_device(target, device), to_device(pred, device)
     _check_window(t)
@@ -204,19 +233,22 @@ def evaluate_pair(target, pred, device, advanced: bool = True, ms_ssim: bool = F
            "mae_norm": stn.mae(), "psnr_norm": stn.psnr(),
            "ssim_norm": _ssim(t, p, float(_rng32(stn.bmin, stn.bmax)), aff)}
     if advanced:
-        ms = lpips(None, None)   # not asked for: empty, as lpips is
-        if ms_ssim:              # on materialised normalize() volumes, as the host path does
-            ms = _ms_ssim(K.normalize(t, aff[0], aff[1]), K.normalize(p, aff[2], aff[3]))
-        out.update({"ms_ssim": ms, "lpips": lpips(None, None), "emd": _emd(t, p, st),
+        ms = lp = lpips()   # not asked for: empty
+        want_lp = lpips_weights is not None and M.lpips_defined(t.shape)
+        if ms_ssim or want_lp:   # on materialised normalize() volumes, as the host path does
+            tn, pn = K.normalize(t, aff[0], aff[1]), K.normalize(p, aff[2], aff[3])
+            ms = _ms_ssim(tn, pn) if ms_ssim else ms
+            lp = lpips(tn, pn, lpips_weights) if want_lp else lp
+        out.update({"ms_ssim": ms, "lpips": lp, "emd": _emd(t, p, st),
                     "ts": _ts(t, p), "cs": st.cs(), "ed": _ed(t, p, st)})
     return out
 
 
-def evaluate_patient(std, gen, vue=None, device: Optional[object] = "cuda", ms_ssim: bool = False):
+def evaluate_patient(std, gen, vue=None, device: Optional[object] = "cuda", ms_ssim: bool = False, lpips_weights=None):
     """modules/metrics.py::evaluate_patient; ``device=None`` runs the host module, anything else
     uploads every series once and keeps the work on that device."""
     if device is None:
-        return M.evaluate_patient(std, gen, vue, ms_ssim)
+        return M.evaluate_patient(std, gen, vue, ms_ssim, lpips_weights)
     up = lambda v: None if v is None else to_device(v, device)
     return M.collect_patient(lambda t, p, adv, **kw: evaluate_pair(t, p, device, adv, **kw), up(std), up(gen), up(vue),
-                             ms_ssim)
+                             ms_ssim, lpips_weights)

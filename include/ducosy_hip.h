@@ -735,6 +735,29 @@ int dcs_met_msssim_level(const float* a, const float* b, int D, int H, int W, co
  * in float64.  H, W >= 2; the outputs alias nothing. */
 int dcs_met_pool2(const float* a, const float* b, float* out_a, float* out_b, int D, int H, int W, void* stream);
 
+/* ---- LPIPS of calculate.py (lpips 0.1.4, net='alex'; modules/metrics.py::lpips_taps states it) ----
+ * Activations are NHWC float32.  Layers 2-5 of the AlexNet trunk run on dcs_conv_rows (bias + ReLU
+ * in its epilogue); these are the first layer and the pass between the convolutions.  A slice's
+ * result depends on that slice alone, whatever N is.  No atomics; bit-identical from run to run. */
+/* AlexNet's first layer (11x11 stride 4 pad 2 -> 64 channels) + ReLU of N slices x [N][H][W],
+ * H, W >= 11, read as t = ((x - off) / div) * 2 - 1 in float32 (div > 0) and, folded in, the scaling
+ * layer on three equal channels: out[N][Ho][Wo][64], Ho = (H - 7) / 4 + 1.  wx: device [121][64], the
+ * tap-major weights of t (sum_c w[o][c] / scale_c).  cb: device [16][64], the bias plus the constant
+ * channel's weights (-sum_c w[o][c] shift_c / scale_c) summed over the taps inside the image, per
+ * class y * 4 + x with 0 = the first two kernel rows (columns) cut, 1 = none, 2 / 3 = the last one /
+ * two cut: the padding is zero AFTER the scaling layer, so the constant is not a bias. */
+int dcs_lpips_stem(const float* x, int N, int H, int W, float off, float div, const float* wx, const float* cb,
+                   float* out, void* stream);
+/* bytes of workspace of dcs_lpips_tap for N slices of h x w maps; 0 for bad dimensions */
+size_t dcs_lpips_tap_workspace_size(int N, int h, int w);
+/* One tap from one read of the ReLU maps fa, fb [N][h][w][C] (C = 64, 192, 256 or 384) of both
+ * volumes: out[n] = sum over the pixels of sum_c lin[c] * (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2
+ * with |f| = sqrt(sum_c f_c^2), in float64 on the float32 samples (the mean divides by h * w); and,
+ * where pool_a / pool_b are given, the 3x3 stride-2 max pool (floor sizes, h, w >= 3) of both maps,
+ * [N][(h-3)/2+1][(w-3)/2+1][C].  lin: device [C]. */
+int dcs_lpips_tap(const float* fa, const float* fb, int N, int h, int w, int C, const float* lin, float* pool_a,
+                  float* pool_b, double* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- difference-map stage (modules/nmodel: the normal-map U-Net run one slice at a time, then
  *      modules/postprocess.py::apply_diffmap) ----
  * Activations are NHWC float32.  The U-Net's 3x3 convolutions run on dcs_conv_rows; these are the

@@ -2,6 +2,7 @@
 """Host against device timing of calculate.py's per-patient metrics (modules/metrics_gpu.py::evaluate_patient).
 
     python scripts/bench_metrics.py [--shape 128x512x512] [--reps 5] [--host_reps 5] [--skip_host] [--ms_ssim]
+                                    [--lpips_weights PATH[,PATH]|random]
 
 One synthetic patient from modules/phantom.py (STD, a generated series = STD + rounded N(0, 20),
 a VUE series) goes through
@@ -21,6 +22,15 @@ metric alone on the STD / generated pair: host time, device time end to end and 
 volumes, and the event time of the level kernel at each of the five levels and of the pooling
 kernel between them (the level kernel reads both volumes once: 8 bytes per voxel of its level;
 the pooling kernel reads both and writes a quarter: 10 bytes per input voxel).
+
+--lpips_weights turns LPIPS on in every leg (its column is compared at 1e-5 relative: both paths hold
+4 x the float32 ATen error against float64, tests/test_gpu_lpips.py, which is below that) and adds
+under "lpips" the metric alone on the STD / generated pair: the host time (ATen, float32), the same
+ATen restatement on the device in float32 on resident volumes (and its convolutions alone, layer
+by layer), the HIP path end to end and resident, the event time of every launch of one resident run
+summed per kernel and layer, and the
+patient end to end and resident without the switch.  ``random`` takes the seeded stand-in weights
+of the tests (modules/lpips_weights.py::random_state_dict).
 """
 import argparse
 import json
@@ -35,10 +45,12 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, os.path.join(ROOT, "ducosy-gan_amd"))
 
+from modules import lpips_weights as LW  # noqa: E402
 from modules import metrics as M  # noqa: E402
 from modules import metrics_gpu as G  # noqa: E402
 from modules import phantom  # noqa: E402
 from modules.hip import metrics as K  # noqa: E402
+from modules.hip import unet as U  # noqa: E402  (the launch timer the LPIPS driver shares)
 
 HBM_PEAK = 8.0e12
 
@@ -115,8 +127,52 @@ def ms_ssim_times(std, gen, reps):
     return out
 
 
+def lpips_aten_device(tn, pn, wdev, step=16):
+    """The host restatement (modules/metrics.py) with ATen on the device in float32, resident volumes."""
+    def chain(x):
+        mn, mx = x.min(), x.max()
+        return (x - mn) / ((mx - mn) + 1e-8) * 2 - 1
+    xa, xb = chain(tn), chain(pn)
+    vals = []
+    with torch.no_grad():
+        for i in range(0, xa.shape[0], step):
+            fa, fb = M.lpips_features(xa[i:i + step], wdev), M.lpips_features(xb[i:i + step], wdev)
+            vals.append(sum(M.lpips_tap(fa[k], fb[k], lin) for k, lin in enumerate(wdev.lins)))
+    return torch.cat(vals).double().cpu().numpy()
+
+
+def lpips_aten_conv_times(D, H, W, wdev, reps, step=16):
+    """ATen's float32 convolution of every layer alone (bias included, no ReLU), per patient: the event
+    time of one call on ``step`` maps times the 2 * D / step calls of lpips_aten_device."""
+    import torch.nn.functional as F
+    out, (h, w) = {}, (H, W)
+    for k, (co, ci, ks, stride, pad, pool) in enumerate(LW.CONVS):
+        if pool:
+            h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+        x = torch.rand(step, ci, h, w, device=wdev.lins[0].device)
+        wt, b = wdev.convs[k]
+        ms = _median_ms(lambda: F.conv2d(x, wt, b, stride=stride, padding=pad), reps)
+        h, w = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+        out[f"conv{ks}x{ks} {ci}->{co} @{h}x{w}"] = round(ms * 2 * D / step, 3)
+    return out
+
+
+def lpips_kernel_times(tn, pn, weights):
+    """Event time of every launch of one resident run, summed per label (kernel, layer and map size)."""
+    G.lpips(tn, pn, weights)
+    torch.cuda.synchronize()
+    U.TIMES = []
+    G.lpips(tn, pn, weights)
+    torch.cuda.synchronize()
+    out = {}
+    for label, a, b in U.TIMES:
+        out[label] = out.get(label, 0.0) + a.elapsed_time(b)
+    U.TIMES = None
+    return {k: round(v, 3) for k, v in out.items()}
+
+
 def _agree(got, want):
-    worst = {"rel": 0.0, "ssim_abs": 0.0, "ms_ssim_abs": 0.0}
+    worst = {"rel": 0.0, "ssim_abs": 0.0, "ms_ssim_abs": 0.0, "lpips_rel": 0.0}
     ok = True
     for k in M.METRICS:
         for gl, wl in zip(got[1][k], want[1][k]):
@@ -126,13 +182,16 @@ def _agree(got, want):
             if not f.any():
                 continue
             err = np.abs(g[f] - w[f])
-            if k == "ms_ssim":
+            if k == "lpips":
+                worst["lpips_rel"] = max(worst["lpips_rel"], float((err / np.abs(w[f])).max()))
+            elif k == "ms_ssim":
                 worst["ms_ssim_abs"] = max(worst["ms_ssim_abs"], float(err.max()))
             elif k.startswith("ssim"):
                 worst["ssim_abs"] = max(worst["ssim_abs"], float(err.max()))
             else:
                 worst["rel"] = max(worst["rel"], float((err / np.maximum(np.abs(w[f]), 1e-300)).max()))
-    return bool(ok and worst["rel"] <= 1e-10 and worst["ssim_abs"] <= 1e-10 and worst["ms_ssim_abs"] <= 1e-9), worst
+    return bool(ok and worst["rel"] <= 1e-10 and worst["ssim_abs"] <= 1e-10 and worst["ms_ssim_abs"] <= 1e-9
+                and worst["lpips_rel"] <= 1e-5), worst
 
 
 def main():
@@ -143,6 +202,8 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--skip_host", action="store_true", help="device times only (no comparison)")
     ap.add_argument("--ms_ssim", action="store_true", help="with MS-SSIM in every leg, and its own times")
+    ap.add_argument("--lpips_weights", default=None, metavar="PATH[,PATH]|random",
+                    help="with LPIPS in every leg, and its own times; 'random': the tests' seeded stand-in weights")
     a = ap.parse_args()
     dev = torch.device(a.device)
     shape = tuple(int(x) for x in a.shape.split("x"))
@@ -152,12 +213,15 @@ def main():
     std, gen, vue = patient(shape)
     print(f"phantom patient {shape} in {time.perf_counter() - t0:.1f} s", flush=True)
     res = {"metric": "evaluate_patient_seconds", "device": torch.cuda.get_device_name(dev), "shape": a.shape,
-           "host_threads": threads, "with_ms_ssim": a.ms_ssim}
+           "host_threads": threads, "with_ms_ssim": a.ms_ssim, "with_lpips": a.lpips_weights is not None}
+    lw = None
+    if a.lpips_weights:
+        lw = LW.from_state_dicts(LW.random_state_dict(3)) if a.lpips_weights == "random" else LW.load(a.lpips_weights)
 
-    def device_run():
+    def device_run(weights=lw):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = G.evaluate_patient(std, gen, vue, device=dev, ms_ssim=a.ms_ssim)
+        out = G.evaluate_patient(std, gen, vue, device=dev, ms_ssim=a.ms_ssim, lpips_weights=weights)
         torch.cuda.synchronize()
         return time.perf_counter() - t0, out
 
@@ -170,7 +234,7 @@ def main():
     res["device_end_to_end_s"] = round(statistics.median(times), 4)
 
     ds, dg, dv = (G.to_device(v, dev) for v in (std, gen, vue))
-    resident = lambda: G.evaluate_patient(ds, dg, dv, device=dev, ms_ssim=a.ms_ssim)
+    resident = lambda weights=lw: G.evaluate_patient(ds, dg, dv, device=dev, ms_ssim=a.ms_ssim, lpips_weights=weights)
     resident()
     torch.cuda.synchronize()
     res["device_resident_ms"] = round(statistics.median(_events(resident) for _ in range(a.reps)), 3)
@@ -188,6 +252,32 @@ def main():
               "device_resident_ms": round(_median_ms(lambda: G.ms_ssim(ds, dg), a.reps), 3)}
         res["kernels"].update(ms_ssim_times(ds, dg, a.reps))
         res["ms_ssim"] = ms
+    if lw is not None:
+        def alone():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            val = G.lpips(G.normalize(G.to_device(std, dev)), G.normalize(G.to_device(gen, dev)), lw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, val
+        alone()
+        runs = [alone() for _ in range(a.reps)]
+        tn, pn = G.normalize(ds), G.normalize(dg)
+        wdev = LW.LpipsWeights([(w.to(dev), b.to(dev)) for w, b in lw.convs], [l.to(dev) for l in lw.lins])
+        aten = lpips_aten_device(tn, pn, wdev)   # warm-up: the library picks its kernels
+        lp = {"device_end_to_end_s": round(statistics.median(r[0] for r in runs), 4), "device_value": runs[-1][1][0],
+              "device_resident_ms": round(_median_ms(lambda: G.lpips(tn, pn, lw), a.reps), 3),
+              "aten_device_f32_resident_ms": round(_median_ms(lambda: lpips_aten_device(tn, pn, wdev), a.reps), 3),
+              "aten_device_f32_value": float(aten.mean()),
+              "chunk_slices": G.L.default_chunk(*ds.shape),
+              "kernels_ms_per_run": lpips_kernel_times(tn, pn, lw),
+              "aten_conv_ms_per_run": lpips_aten_conv_times(*ds.shape, wdev, a.reps)}
+        lp["hip_over_aten_resident"] = round(lp["aten_device_f32_resident_ms"] / lp["device_resident_ms"], 2)
+        without = [device_run(None)[0] for _ in range(a.reps + 1)][1:]
+        lp["patient_without_switch"] = {"device_end_to_end_s": round(statistics.median(without), 4),
+                                        "device_resident_ms": round(_median_ms(lambda: resident(None), a.reps), 3)}
+        res["lpips"] = lp
+        print("lpips:", json.dumps(lp), flush=True)
+        del tn, pn
     del ds, dg, dv
     print("device:", json.dumps({k: res[k] for k in ("device_end_to_end_s", "device_resident_ms")}), flush=True)
 
@@ -195,7 +285,7 @@ def main():
         times = []
         for i in range(a.host_reps + 1):
             t0 = time.perf_counter()
-            want = G.evaluate_patient(std, gen, vue, device=None, ms_ssim=a.ms_ssim)
+            want = G.evaluate_patient(std, gen, vue, device=None, ms_ssim=a.ms_ssim, lpips_weights=lw)
             dt = time.perf_counter() - t0
             print(f"host run {i}{' (warm-up)' if i == 0 else ''}: {dt:.2f} s", flush=True)
             if i:
@@ -212,6 +302,16 @@ def main():
                 times.append(time.perf_counter() - t0)
             res["ms_ssim"].update({"host_s": round(statistics.median(times[1:]), 3), "host_value": val[0],
                                    "abs_error": abs(val[0] - res["ms_ssim"]["device_value"])})
+        if lw is not None:
+            tn, pn = M.normalize(std), M.normalize(gen)
+            times = []
+            for i in range(a.host_reps + 1):
+                t0 = time.perf_counter()
+                val = M.lpips(tn, pn, lw)
+                times.append(time.perf_counter() - t0)
+                print(f"host lpips run {i}{' (warm-up)' if i == 0 else ''}: {times[-1]:.2f} s", flush=True)
+            res["lpips"].update({"host_s": round(statistics.median(times[1:]), 3), "host_value": val[0],
+                                 "rel_error": abs(val[0] - res["lpips"]["device_value"]) / val[0]})
     print(json.dumps(res))
     if not a.skip_host and not res["agree"]:
         sys.exit(1)
