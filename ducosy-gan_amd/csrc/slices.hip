@@ -1,15 +1,17 @@
 // Slice-series kernels of the resident inference path (generate.py --pipeline resident,
 // modules/inference.py::translate_volume_device) on gfx950: the map from the two Generators'
-// outputs to stored values fused with the HU-range merge, and the two resizes of series whose
-// slice size differs from the network's (antialiased bilinear for images, nearest for masks).
+// outputs to stored values fused with the HU-range merge (translate_merge) or with the
+// enhancement-difference merge (translate_enhance), and the two resizes of series whose slice size
+// differs from the network's (antialiased bilinear for images, nearest for masks).
 //
-// translate_merge repeats the host's float32 operations one IEEE operation per step
-// (inference.stored_from_output, inference.synthesize), and the antialiased resize accumulates
-// acc = acc + x * w in tap order as two roundings, so contraction is off for this whole file.
+// translate_merge and translate_enhance repeat the host's float32 operations one IEEE operation
+// per step (inference.stored_from_output, inference.synthesize, inference.synthesize_enhancement),
+// and the antialiased resize accumulates acc = acc + x * w in tap order as two roundings, so
+// contraction is off for this whole file.
 //
-// All kernels are HBM-bound streams.  translate_merge and the vertical resize pass own one 16-byte
-// vector of float32 along x per thread when the row length and the pointers allow it, else one
-// element.  The vertical pass reads its taps straight from global memory (neighbouring outputs
+// All kernels are HBM-bound streams.  The two merges and the vertical resize pass own one 16-byte
+// vector of float32 along x per thread when the row length (the plane size for translate_enhance)
+// and the pointers allow it, else one element.  The vertical pass reads its taps straight from global memory (neighbouring outputs
 // share the lines, which come from L2); the horizontal pass stages the input segment of a run of
 // output columns in LDS.
 #include "common.hpp"
@@ -70,6 +72,53 @@ __global__ void __launch_bounds__(ST) translate_merge_kernel(
     if (lung_out) *reinterpret_cast<VP*>(lung_out + e) = lo;
     if (merged) *reinterpret_cast<VP*>(merged + e) = mo;
     if (merged_f32) *reinterpret_cast<VF*>(merged_f32 + e) = mf;
+}
+
+// inference.synthesize_enhancement for one voxel (the same rule as volume.hip's): r = f32(raw),
+// hs / hl the HU of the two translations.  Both comparisons strict; soft tissue first, then lung.
+__device__ __forceinline__ float enhance(float r, float hs, float hl, float a, float b, float thr, float min_hu) {
+    const float hr = r * a + b;
+    const float es = hs - hr, el = hl - hr;
+    const bool valid = hr > min_hu;
+    float m = r;
+    if (es > thr && valid) m = m + __fdiv_rn(es, a);
+    if (el > thr && valid) m = m + __fdiv_rn(el, a);
+    return m;
+}
+
+// translate_merge_kernel's map to stored values, then the enhancement rule on the HU of those
+// stored values (what the staged path reads back from its working series).
+template <typename TP, int VEC>
+__global__ void __launch_bounds__(ST) translate_enhance_kernel(
+    const TP* __restrict__ raw, const float* __restrict__ slope, const float* __restrict__ intercept,
+    const float* __restrict__ ys, const float* __restrict__ yl, int64_t nvec, int64_t S, float slo, float sspan,
+    float llo, float lspan, float thr, float min_hu, TP* __restrict__ soft_out, TP* __restrict__ lung_out,
+    float* __restrict__ merged_f32) {
+    const int64_t i = (int64_t)blockIdx.x * ST + threadIdx.x;
+    if (i >= nvec) return;
+    const int64_t e = i * VEC;
+    const int64_t z = e / S;
+    const float a = slope[z], b = intercept[z];
+    using VP = SVec<TP, VEC>;
+    using VF = SVec<float, VEC>;
+    const VP r = *reinterpret_cast<const VP*>(raw + e);
+    const VF s = *reinterpret_cast<const VF*>(ys + e);
+    const VF g = *reinterpret_cast<const VF*>(yl + e);
+    VP so, lo;
+    VF mf;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        const float hs = ((s.v[v] + 1.0f) / 2.0f) * sspan + slo;
+        const float hl = ((g.v[v] + 1.0f) / 2.0f) * lspan + llo;
+        const TP ps = to_stored<TP>(__fdiv_rn(hs - b, a));
+        const TP pl = to_stored<TP>(__fdiv_rn(hl - b, a));
+        so.v[v] = ps;
+        lo.v[v] = pl;
+        mf.v[v] = enhance((float)r.v[v], (float)ps * a + b, (float)pl * a + b, a, b, thr, min_hu);
+    }
+    if (soft_out) *reinterpret_cast<VP*>(soft_out + e) = so;
+    if (lung_out) *reinterpret_cast<VP*>(lung_out + e) = lo;
+    *reinterpret_cast<VF*>(merged_f32 + e) = mf;
 }
 
 // Horizontal pass of the antialiased resize: one block per run of HT output columns of one row.
@@ -178,6 +227,22 @@ static void launch_translate_merge(const void* raw, const float* slope, const fl
                            static_cast<TP*>(lo), static_cast<TP*>(mo), mf);
 }
 
+template <typename TP>
+static void launch_translate_enhance(const void* raw, const float* slope, const float* intercept, const float* ys,
+                                     const float* yl, int64_t n, int64_t S, const float* rg, void* so, void* lo,
+                                     float* mf, hipStream_t s) {
+    const bool vec = S % 4 == 0 && al(raw, 8) && al(ys, 16) && al(yl, 16) && al(so, 8) && al(lo, 8) && al(mf, 16);
+    const TP* r = static_cast<const TP*>(raw);
+    if (vec)
+        hipLaunchKernelGGL((translate_enhance_kernel<TP, 4>), dim3(sblocks(n / 4)), dim3(ST), 0, s, r, slope, intercept,
+                           ys, yl, n / 4, S, rg[0], rg[1], rg[2], rg[3], rg[4], rg[5], static_cast<TP*>(so),
+                           static_cast<TP*>(lo), mf);
+    else
+        hipLaunchKernelGGL((translate_enhance_kernel<TP, 1>), dim3(sblocks(n)), dim3(ST), 0, s, r, slope, intercept,
+                           ys, yl, n, S, rg[0], rg[1], rg[2], rg[3], rg[4], rg[5], static_cast<TP*>(so),
+                           static_cast<TP*>(lo), mf);
+}
+
 }  // namespace dcs
 
 using namespace dcs;
@@ -212,6 +277,37 @@ extern "C" int dcs_vol_translate_merge(const void* raw, int stored_dtype, const 
         launch_translate_merge<uint16_t>(raw, slope, intercept, y_soft, y_lung, n, S, W, rg, soft_stored, lung_stored,
                                          merged, merged_f32, s);
     return check_launch("vol_translate_merge");
+}
+
+extern "C" int dcs_vol_translate_enhance(const void* raw, int stored_dtype, const float* slope, const float* intercept,
+                                         const float* y_soft, const float* y_lung, int D, int H, int W, float soft_lo,
+                                         float soft_span, float lung_lo, float lung_span, float threshold,
+                                         float min_hu, void* soft_stored, void* lung_stored, float* merged_f32,
+                                         void* stream) {
+    if (!raw || !slope || !intercept || !y_soft || !y_lung || !merged_f32)
+        return fail(DCS_E_INVALID, "vol_translate_enhance: null pointer");
+    if (D <= 0 || H <= 0 || W <= 0 || D >= (1 << 30) || H >= (1 << 30) || W >= (1 << 30) ||
+        (long double)D * H * W >= (long double)(1ll << 38))
+        return fail(DCS_E_INVALID, "vol_translate_enhance: bad dimensions");
+    if (stored_dtype != DCS_VOL_I16 && stored_dtype != DCS_VOL_U16)
+        return fail(DCS_E_INVALID, "vol_translate_enhance: stored dtype must be int16 or uint16");
+    if (!al(raw, 2) || !al(soft_stored, 2) || !al(lung_stored, 2) || !al(merged_f32, 4) || !al(y_soft, 4) ||
+        !al(y_lung, 4) || !al(slope, 4) || !al(intercept, 4))
+        return fail(DCS_E_INVALID, "vol_translate_enhance: misaligned pointer");
+    const void* outs[3] = {soft_stored, lung_stored, merged_f32};
+    for (const void* o : outs)
+        if (o && (o == raw || o == y_soft || o == y_lung))
+            return fail(DCS_E_INVALID, "vol_translate_enhance: an output aliases an input");
+    const int64_t S = (int64_t)H * W, n = S * D;
+    const float rg[6] = {soft_lo, soft_span, lung_lo, lung_span, threshold, min_hu};
+    hipStream_t s = as_stream(stream);
+    if (stored_dtype == DCS_VOL_I16)
+        launch_translate_enhance<int16_t>(raw, slope, intercept, y_soft, y_lung, n, S, rg, soft_stored, lung_stored,
+                                          merged_f32, s);
+    else
+        launch_translate_enhance<uint16_t>(raw, slope, intercept, y_soft, y_lung, n, S, rg, soft_stored, lung_stored,
+                                           merged_f32, s);
+    return check_launch("vol_translate_enhance");
 }
 
 extern "C" int dcs_resize_aa(const float* in, float* out, float* tmp, int NC, int H, int W, int oh, int ow,

@@ -1,7 +1,8 @@
 // Volume post-processing of generate.py's synthesis stage on gfx950 (modules/postprocess.py and
 // modules/inference.py::synthesize / smooth_volume on the host): separable Gaussian along one
 // axis, z median, z Kalman, exact min/max, the fused unsharp mask + threshold restore + int16
-// cast, and the HU-range merge.  Dense [D][H][W] volumes, x fastest.
+// cast, the HU-range merge and the enhancement-difference merge (synthesize_enhancement).  Dense
+// [D][H][W] volumes, x fastest.
 //
 // Every kernel reproduces the host arithmetic bit for bit: scipy's correlate1d (symmetric
 // weights) runs in double as  tmp = x[l]*w[r];  tmp += (x[l+ii] + x[l-ii]) * w[ii+r]  for
@@ -297,6 +298,41 @@ __global__ void __launch_bounds__(VT) merge_kernel(const TP* __restrict__ raw, c
     if (out_f32) *reinterpret_cast<Vec<float, VEC>*>(out_f32 + e) = f;
 }
 
+// Enhancement-difference merge (inference.synthesize_enhancement on every slice), float32, one
+// IEEE operation per step: the NCCT value plus each translation's HU gain over it, where that gain
+// exceeds thr and the NCCT HU exceeds min_hu (both strict); soft tissue first, then lung.
+template <typename TP, int VEC>
+__global__ void __launch_bounds__(VT) merge_enhance_kernel(const TP* __restrict__ raw, const TP* __restrict__ soft,
+                                                           const TP* __restrict__ lung,
+                                                           const float* __restrict__ slope,
+                                                           const float* __restrict__ intercept, int64_t nvec,
+                                                           int64_t S, float thr, float min_hu,
+                                                           float* __restrict__ out_f32) {
+    const int64_t i = (int64_t)blockIdx.x * VT + threadIdx.x;
+    if (i >= nvec) return;
+    const int64_t e = i * VEC;
+    const int64_t z = e / S;
+    const float a = slope[z], b = intercept[z];
+    using VP = Vec<TP, VEC>;
+    const VP r = *reinterpret_cast<const VP*>(raw + e);
+    const VP s = *reinterpret_cast<const VP*>(soft + e);
+    const VP g = *reinterpret_cast<const VP*>(lung + e);
+    Vec<float, VEC> f;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        const float rv = (float)r.v[v];
+        const float hr = rv * a + b;
+        const float es = ((float)s.v[v] * a + b) - hr;
+        const float el = ((float)g.v[v] * a + b) - hr;
+        const bool valid = hr > min_hu;
+        float m = rv;
+        if (es > thr && valid) m = m + __fdiv_rn(es, a);
+        if (el > thr && valid) m = m + __fdiv_rn(el, a);
+        f.v[v] = m;
+    }
+    *reinterpret_cast<Vec<float, VEC>*>(out_f32 + e) = f;
+}
+
 static bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // dims accepted by every volume entry point: positive, each < 2^30 (reflect_idx doubles one),
@@ -373,6 +409,21 @@ static void launch_merge(const void* raw, const void* soft, const void* lung, co
     else
         hipLaunchKernelGGL((merge_kernel<TP, 1>), dim3(blocks_for(n)), dim3(VT), 0, s, r, so, lu, slope, intercept, n,
                            S, slo, shi, llo, lhi, static_cast<TP*>(out), out_f32);
+}
+
+// one 16-byte float vector of the output per thread: 4 stored values (8 bytes) of each input
+template <typename TP>
+static void launch_merge_enhance(const void* raw, const void* soft, const void* lung, const float* slope,
+                                 const float* intercept, int64_t n, int64_t S, float thr, float min_hu, float* out_f32,
+                                 hipStream_t s) {
+    const bool vec = S % 4 == 0 && aligned(raw, 8) && aligned(soft, 8) && aligned(lung, 8) && aligned(out_f32, 16);
+    const TP *r = static_cast<const TP*>(raw), *so = static_cast<const TP*>(soft), *lu = static_cast<const TP*>(lung);
+    if (vec)
+        hipLaunchKernelGGL((merge_enhance_kernel<TP, 4>), dim3(blocks_for(n / 4)), dim3(VT), 0, s, r, so, lu, slope,
+                           intercept, n / 4, S, thr, min_hu, out_f32);
+    else
+        hipLaunchKernelGGL((merge_enhance_kernel<TP, 1>), dim3(blocks_for(n)), dim3(VT), 0, s, r, so, lu, slope,
+                           intercept, n, S, thr, min_hu, out_f32);
 }
 
 }  // namespace dcs
@@ -504,4 +555,26 @@ extern "C" int dcs_vol_merge(const void* raw, const void* soft, const void* lung
         launch_merge<uint16_t>(raw, soft, lung, slope, intercept, n, S, soft_lo, soft_hi, lung_lo, lung_hi, out,
                                out_f32, s);
     return check_launch("vol_merge");
+}
+
+extern "C" int dcs_vol_merge_enhance(const void* raw, const void* soft, const void* lung, int stored_dtype,
+                                     const float* slope, const float* intercept, int D, int H, int W, float threshold,
+                                     float min_hu, float* out_f32, void* stream) {
+    if (!raw || !soft || !lung || !slope || !intercept || !out_f32)
+        return fail(DCS_E_INVALID, "vol_merge_enhance: null pointer");
+    if (!dims_ok(D, H, W)) return fail(DCS_E_INVALID, "vol_merge_enhance: bad dimensions");
+    if (stored_dtype != DCS_VOL_I16 && stored_dtype != DCS_VOL_U16)
+        return fail(DCS_E_INVALID, "vol_merge_enhance: stored dtype must be int16 or uint16");
+    if (!aligned(raw, 2) || !aligned(soft, 2) || !aligned(lung, 2) || !aligned(out_f32, 4) || !aligned(slope, 4) ||
+        !aligned(intercept, 4))
+        return fail(DCS_E_INVALID, "vol_merge_enhance: misaligned pointer");
+    if (out_f32 == raw || out_f32 == soft || out_f32 == lung)
+        return fail(DCS_E_INVALID, "vol_merge_enhance: the output aliases an input");
+    const int64_t S = (int64_t)H * W, n = S * D;
+    hipStream_t s = as_stream(stream);
+    if (stored_dtype == DCS_VOL_I16)
+        launch_merge_enhance<int16_t>(raw, soft, lung, slope, intercept, n, S, threshold, min_hu, out_f32, s);
+    else
+        launch_merge_enhance<uint16_t>(raw, soft, lung, slope, intercept, n, S, threshold, min_hu, out_f32, s);
+    return check_launch("vol_merge_enhance");
 }

@@ -1,4 +1,4 @@
-"""Inference entry point — mirror of the reference's generate.py (generate(), synthesis()).
+"""Inference entry point — mirror of the reference's generate.py (generate(), synthesis(), synthesis_test()).
 
     python ducosy-gan_amd/generate.py --input_dir_root ... --dataset_names NAME \
         --model_path_soft ckpt_soft.pth --model_path_lung ckpt_lung.pth
@@ -22,7 +22,13 @@ Differences from the reference, all deliberate:
   * --apply_diffmap runs the reference's difference-map stage (commented out in its synthesis()):
     the normal-map U-Net of --nmodel_path predicts a contrast difference map from the NCCT HU
     series (modules/nmodel, csrc/unet.hip) and apply_diffmap adds it to the merged volume before
-    the smoothing; --save_diff keeps the map as diff.npy in the patient's working directory.
+    the smoothing; --save_diff keeps the map as diff.npy in the patient's working directory;
+  * --synthesis enhancement runs the reference's second synthesis stage (synthesis_test, never
+    called by its __main__) in place of synthesis(): the NCCT is kept everywhere, and where a model
+    raised the HU by more than --enhancement_threshold (5) and the NCCT is above
+    --enhancement_min_hu (-400) that model's gain is added; the series is written as
+    "DuCoSyGAN sCECT v3".  Staged on the host, staged with --postprocess_device cuda
+    (csrc/volume.hip) and --pipeline resident (csrc/slices.hip) write identical files.
 DICOM reading/writing uses modules/dicom.py (pydicom is not installed in this image).
 """
 import argparse
@@ -40,7 +46,8 @@ import torch  # noqa: E402
 
 from modules.inference import (MASK_TYPES, _conditioning, hu_from_stored, normalise_hu,  # noqa: E402,F401
                                smooth_volume, smooth_volume_device, stored_from_output, synthesize,
-                               synthesize_volume, translate_slices, translate_volume_device)
+                               synthesize_enhancement, synthesize_volume, translate_slices,
+                               translate_volume_device)
 from modules.model import Generator  # noqa: E402
 from modules.nmodel import load_model, predict_volume  # noqa: E402
 from modules.postprocess import apply_diffmap  # noqa: E402
@@ -125,14 +132,36 @@ def generate(args, soft_tissue_args=None, lung_args=None):
     print("\nGeneration complete.")
 
 
+DESCRIPTIONS = {"range": "DuCoSyGAN sCECT v2", "enhancement": "DuCoSyGAN sCECT v3"}
+
+
+def _rescale(d):
+    return getattr(d, "RescaleSlope", 1), getattr(d, "RescaleIntercept", 0)
+
+
 def synthesis(args, soft_tissue_args=None, lung_args=None):
     """generate.py:137-297 (same signature): merge the two translations inside their HU ranges
     over the NCCT, z-smooth the volume (modules/postprocess.py) and write
     output/{dataset}/{patient}/{idx:04d}.dcm."""
+    _synthesis_stage(args, soft_tissue_args, lung_args, "range")
+
+
+def synthesis_test(args, soft_tissue_args=None, lung_args=None):
+    """generate.py:302-477 (same signature), "sCECT v3": keep the NCCT and add each translation's
+    HU gain where it exceeds --enhancement_threshold and the NCCT HU exceeds --enhancement_min_hu
+    (modules/inference.py::synthesize_enhancement); then the same smoothing, header edits and
+    files as synthesis().  Honours --postprocess_device, --apply_diffmap, --save_diff and
+    --diffmap_threshold like synthesis()."""
+    _synthesis_stage(args, soft_tissue_args, lung_args, "enhancement")
+
+
+def _synthesis_stage(args, soft_tissue_args, lung_args, mode):
+    """The staged synthesis stage; ``mode``: "range" (synthesis) or "enhancement" (synthesis_test)."""
     from modules import dicom
     sa, la = _model_args(args, soft_tissue_args, lung_args)
     post_dev = f"cuda:{args.gpu_id}" if getattr(args, "postprocess_device", "cpu") == "cuda" else None
     nmodel = _load_nmodel(args, torch.device(f"cuda:{args.gpu_id}"))
+    thr_e, min_hu_e = getattr(args, "enhancement_threshold", 5.0), getattr(args, "enhancement_min_hu", -400.0)
     for dataset_name in args.dataset_names:
         working_dir = os.path.join(args.working_dir_root, dataset_name)
         output_dir = os.path.join(args.output_dir_root, dataset_name)
@@ -141,25 +170,38 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
             if not all(lists) or len({len(x) for x in lists}) != 1:
                 print(f"Skipping {patient_dir}: missing or mismatched slices")
                 continue
-            merged, series, rescale, raw_hu_series = [], [], [], []
+            merged, series, rescale, raw_hu_series, own_pairs = [], [], [], [], []
             for rp, sp, lp in zip(*lists):
                 raw, st, lg = dicom.dcmread(rp), dicom.dcmread(sp), dicom.dcmread(lp)
                 if nmodel is not None:
-                    raw_hu_series.append(hu_from_stored(raw.pixel_array, getattr(raw, "RescaleSlope", 1),
-                                                        getattr(raw, "RescaleIntercept", 0)))
+                    raw_hu_series.append(hu_from_stored(raw.pixel_array, *_rescale(raw)))
+                if mode == "enhancement":  # the reference reads each translated file's own rescale pair
+                    own_pairs.append((_rescale(st), _rescale(lg)))
                 if post_dev is not None:
                     series.append((raw.pixel_array, st.pixel_array, lg.pixel_array))
-                    rescale.append((getattr(raw, "RescaleSlope", 1), getattr(raw, "RescaleIntercept", 0)))
+                    rescale.append(_rescale(raw))
                     continue
-                raw_hu = hu_from_stored(raw.pixel_array, getattr(raw, "RescaleSlope", 1),
-                                        getattr(raw, "RescaleIntercept", 0))
+                if mode == "enhancement":
+                    merged.append(synthesize_enhancement(raw.pixel_array, st.pixel_array, lg.pixel_array,
+                                                         *_rescale(raw), thr_e, min_hu_e, *own_pairs[-1]))
+                    continue
+                raw_hu = hu_from_stored(raw.pixel_array, *_rescale(raw))
                 merged.append(synthesize(raw.pixel_array, raw_hu, st.pixel_array, lg.pixel_array,
                                          (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max)))
             if post_dev is not None:
                 raw_v, soft_v, lung_v = (np.stack(x) for x in zip(*series))
-                on_dev = synthesize_volume(raw_v, [a for a, _ in rescale], [b for _, b in rescale], soft_v, lung_v,
-                                           (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max), device=post_dev,
-                                           keep_on_device=True)
+                f32 = lambda pair: tuple(np.float32(v) for v in pair)
+                if any(f32(p) != f32(r) for own, r in zip(own_pairs, rescale) for p in own):
+                    # the kernel reads all three series with the NCCT's pair
+                    print(f"{os.path.basename(patient_dir)}: the translated series carry their own rescale pairs; "
+                          "merging on the host")
+                    on_dev = torch.from_numpy(np.stack([
+                        synthesize_enhancement(r, s, g, a, b, thr_e, min_hu_e, *own)
+                        for r, s, g, (a, b), own in zip(raw_v, soft_v, lung_v, rescale, own_pairs)])).to(post_dev)
+                else:
+                    on_dev = synthesize_volume(raw_v, [a for a, _ in rescale], [b for _, b in rescale], soft_v, lung_v,
+                                               (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max), device=post_dev,
+                                               keep_on_device=True, mode=mode, threshold=thr_e, min_hu=min_hu_e)
             if nmodel is not None:  # the difference-map stage: after the merge, before the smoothing
                 diff = predict_volume(nmodel, np.stack(raw_hu_series), f"cuda:{args.gpu_id}")
                 if getattr(args, "save_diff", False):
@@ -183,7 +225,7 @@ def synthesis(args, soft_tissue_args=None, lung_args=None):
                 o.add_new((0x0028, 0x0106), vr, int(px.min()))
                 o.add_new((0x0028, 0x0107), vr, int(px.max()))
                 o.WindowWidth, o.WindowCenter = 1250, -375.0   # generate.py:279-282
-                o.SeriesDescription = "DuCoSyGAN sCECT v2"
+                o.SeriesDescription = DESCRIPTIONS[mode]
                 o.save_as(os.path.join(out_base, f"{idx:04d}.dcm"))
     print("\nSynthesis complete.")
 
@@ -217,6 +259,7 @@ def generate_synthesis(args, soft_tissue_args=None, lung_args=None):
     save_diff = nmodel is not None and bool(getattr(args, "save_diff", False))
     batch = int(getattr(args, "slice_batch", 16))
     write_working = bool(getattr(args, "write_working", False))
+    mode = getattr(args, "synthesis", "range")
     soft_range, lung_range = (sa.hu_min, sa.hu_max), (la.hu_min, la.hu_max)
     for dataset_name in args.dataset_names:
         input_dir = os.path.join(args.input_dir_root, dataset_name)
@@ -247,6 +290,9 @@ def generate_synthesis(args, soft_tissue_args=None, lung_args=None):
                 raw = np.stack([pixels[i] for i in idxs])
                 stage = {} if nmodel is None else dict(nmodel=nmodel, want_diff=save_diff,
                                                        diffmap_threshold=getattr(args, "diffmap_threshold", 8))
+                if mode == "enhancement":
+                    stage.update(synthesis=mode, enhancement_threshold=getattr(args, "enhancement_threshold", 5.0),
+                                 enhancement_min_hu=getattr(args, "enhancement_min_hu", -400.0))
                 res = translate_volume_device(
                     soft, lung, raw, [getattr(dcms[i], "RescaleSlope", 1) for i in idxs],
                     [getattr(dcms[i], "RescaleIntercept", 0) for i in idxs], soft_range, lung_range,
@@ -272,7 +318,7 @@ def generate_synthesis(args, soft_tissue_args=None, lung_args=None):
                     o.add_new((0x0028, 0x0106), vr, int(px.min()))
                     o.add_new((0x0028, 0x0107), vr, int(px.max()))
                     o.WindowWidth, o.WindowCenter = 1250, -375.0   # generate.py:279-282
-                    o.SeriesDescription = "DuCoSyGAN sCECT v2"
+                    o.SeriesDescription = DESCRIPTIONS[mode]
                     o.save_as(os.path.join(out_base, f"{i:04d}.dcm"))
     print("\nGeneration and synthesis complete.")
 
@@ -314,6 +360,13 @@ def get_args(argv=None):
     p.add_argument("--save_diff", action="store_true",
                    help="--apply_diffmap: write the predicted difference map as diff.npy into the patient's working "
                         "directory")
+    p.add_argument("--synthesis", choices=["range", "enhancement"], default="range",
+                   help="range: overwrite the NCCT inside each model's HU range (synthesis, sCECT v2); enhancement: "
+                        "keep the NCCT and add each model's HU gain where it is significant (synthesis_test, sCECT v3)")
+    p.add_argument("--enhancement_threshold", type=float, default=5.0,
+                   help="--synthesis enhancement: a model's HU gain over the NCCT must exceed this to be added")
+    p.add_argument("--enhancement_min_hu", type=float, default=-400.0,
+                   help="--synthesis enhancement: voxels whose NCCT HU does not exceed this are left as they are")
     return p.parse_args(argv)
 
 
@@ -324,8 +377,8 @@ if __name__ == "__main__":
         generate_synthesis(a, soft_a, lung_a)
     else:
         if a.pipeline == "resident":
-            print("--skip_convert: running the staged synthesis() on the working series (--pipeline resident "
+            print("--skip_convert: running the staged synthesis stage on the working series (--pipeline resident "
                   "has no stage of its own to skip to)")
         if not a.skip_convert:
             generate(a, soft_a, lung_a)
-        synthesis(a, soft_a, lung_a)
+        (synthesis_test if a.synthesis == "enhancement" else synthesis)(a, soft_a, lung_a)

@@ -183,6 +183,9 @@ SIGNATURES = {
                               P, P, P]),
     "dcs_vol_translate_merge": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
                                         c_float, c_float, P, P, P, P, P]),
+    "dcs_vol_merge_enhance": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_float, c_float, P, P]),
+    "dcs_vol_translate_enhance": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float,
+                                          c_float, c_float, c_float, P, P, P, P]),
     "dcs_resize_aa": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P]),
     "dcs_resize_nearest": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "dcs_met_workspace_size": (c_size_t, [c_int, c_int, c_int]),

@@ -1,5 +1,6 @@
 """Device wrappers of the slice-series kernels (csrc/slices.hip): the antialiased and nearest
-resizes of [N,C,H,W] float32 tensors and the fused model-output -> stored-value -> HU-range merge.
+resizes of [N,C,H,W] float32 tensors and the fused model-output -> stored-value -> merge kernels
+(the HU-range merge and the enhancement-difference merge).
 
 Conventions of modules/hip/volume.py: device tensors only (no CPU fallback), a bad argument
 raises, kernels go to the current stream, ``with torch.cuda.device(...)`` is left to the caller.
@@ -169,3 +170,41 @@ def translate_merge(raw: torch.Tensor, slope: torch.Tensor, intercept: torch.Ten
              _p(y_soft), _p(y_lung), D, H, W, f(slo), f(shi), f(shi - slo), f(llo), f(lhi), f(lhi - llo),
              _p(so), _p(lo), _p(mo), _p(mf), _stream())
     return so, lo, mo, mf
+
+
+def translate_enhance(raw: torch.Tensor, slope: torch.Tensor, intercept: torch.Tensor, y_soft: torch.Tensor,
+                      y_lung: torch.Tensor, soft_range: Tuple[float, float], lung_range: Tuple[float, float],
+                      threshold: float = 5.0, min_hu: float = -400.0, unsigned: bool = False,
+                      want_stored: bool = False):
+    """modules/inference.py::stored_from_output of both Generators' outputs and
+    ``synthesize_enhancement`` of the resulting stored values on every slice, in one kernel.
+    Operands as ``translate_merge``.  Returns (soft stored, lung stored, merged as float32); the two
+    stored series are None without ``want_stored``."""
+    for t, dt, name in ((raw, torch.int16, "raw"), (y_soft, torch.float32, "y_soft"),
+                        (y_lung, torch.float32, "y_lung")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"translate_enhance: {name}: device tensor required (no CPU fallback)")
+        if t.dtype != dt:
+            raise RuntimeError(f"translate_enhance: {name}: unsupported dtype {t.dtype}")
+    if raw.dim() != 3 or raw.numel() == 0:
+        raise ValueError("translate_enhance: [D,H,W] volume required")
+    D, H, W = raw.shape
+    if y_soft.numel() != raw.numel() or y_lung.numel() != raw.numel():
+        raise ValueError("translate_enhance: the model outputs differ in size from the raw series")
+    if y_soft.device != raw.device or y_lung.device != raw.device:
+        raise ValueError("translate_enhance: operands on different devices")
+    raw, y_soft, y_lung = raw.contiguous(), y_soft.contiguous(), y_lung.contiguous()
+    slope = slope.to(device=raw.device, dtype=torch.float32).reshape(-1).contiguous()
+    intercept = intercept.to(device=raw.device, dtype=torch.float32).reshape(-1).contiguous()
+    if slope.numel() != D or intercept.numel() != D:
+        raise ValueError("translate_enhance: one slope/intercept per slice")
+    so = torch.empty_like(raw) if want_stored else None
+    lo = torch.empty_like(raw) if want_stored else None
+    mf = torch.empty(raw.shape, dtype=torch.float32, device=raw.device)
+    f = lambda v: float(np.float32(v))
+    (slo, shi), (llo, lhi) = soft_range, lung_range
+    # hi - lo is formed before the float32 rounding, as stored_from_output's (hu_max - hu_min)
+    lib.call("dcs_vol_translate_enhance", _p(raw), lib.VOL_U16 if unsigned else lib.VOL_I16, _p(slope), _p(intercept),
+             _p(y_soft), _p(y_lung), D, H, W, f(slo), f(shi - slo), f(llo), f(lhi - llo), f(threshold), f(min_hu),
+             _p(so), _p(lo), _p(mf), _stream())
+    return so, lo, mf

@@ -170,3 +170,30 @@ def merge_hu_ranges(raw: torch.Tensor, soft: torch.Tensor, lung: torch.Tensor, s
              _p(intercept), D, H, W, f(soft_range[0]), f(soft_range[1]), f(lung_range[0]), f(lung_range[1]),
              _p(out), _p(f32), _stream())
     return out, f32
+
+
+def merge_enhancement(raw: torch.Tensor, soft: torch.Tensor, lung: torch.Tensor, slope: torch.Tensor,
+                      intercept: torch.Tensor, threshold: float = 5.0, min_hu: float = -400.0,
+                      unsigned: bool = False) -> torch.Tensor:
+    """modules/inference.py::synthesize_enhancement on every slice of three stored-value volumes
+    (int16 tensors; ``unsigned``: the bits are uint16), all three read with the NCCT's rescale pair.
+    slope / intercept: float32 [D] device tensors.  Returns the merged values as float32."""
+    raw = _vol(raw, "merge_enhancement", (torch.int16,))
+    soft = _vol(soft, "merge_enhancement", (torch.int16,))
+    lung = _vol(lung, "merge_enhancement", (torch.int16,))
+    D, H, W = raw.shape
+    if soft.shape != raw.shape or lung.shape != raw.shape:
+        raise ValueError("merge_enhancement: the three series differ in shape")
+    if soft.device != raw.device or lung.device != raw.device:
+        raise ValueError("merge_enhancement: operands on different devices")
+    if raw.numel() == 0:
+        raise ValueError("merge_enhancement: empty volume")
+    slope = slope.to(device=raw.device, dtype=torch.float32).reshape(-1).contiguous()
+    intercept = intercept.to(device=raw.device, dtype=torch.float32).reshape(-1).contiguous()
+    if slope.numel() != D or intercept.numel() != D:
+        raise ValueError("merge_enhancement: one slope/intercept per slice")
+    out = torch.empty(raw.shape, dtype=torch.float32, device=raw.device)
+    f = lambda v: float(np.float32(v))
+    lib.call("dcs_vol_merge_enhance", _p(raw), _p(soft), _p(lung), lib.VOL_U16 if unsigned else lib.VOL_I16,
+             _p(slope), _p(intercept), D, H, W, f(threshold), f(min_hu), _p(out), _stream())
+    return out

@@ -2,7 +2,8 @@
 
 Mirrors the array arithmetic of modules/preprocess.py:68-113 (HU transform, clipping,
 [-1, 1] normalisation, inverse mapping to stored pixel values) and generate.py:144-236 (the
-complementary HU-range synthesis), and batches the Generator forward over slices (the
+complementary HU-range synthesis) and generate.py:302-477 (the enhancement-difference synthesis),
+and batches the Generator forward over slices (the
 reference runs one slice per call, generate.py:108-111).  DICOM parsing stays on the host
 (pydicom, imported lazily by generate.py); nothing here needs it, so the math is testable
 without it.
@@ -100,7 +101,8 @@ def _conditioning(g, kind, hu_slices, device, mask_types=MASK_TYPES):
 def translate_volume_device(soft_model, lung_model, raw_stored, slopes, intercepts,
                             soft_range: Tuple[float, float], lung_range: Tuple[float, float], img_size: int,
                             batch: int = 16, device="cuda", mask_types=MASK_TYPES, want_stored: bool = False,
-                            nmodel=None, diffmap_threshold=8, want_diff: bool = False):
+                            nmodel=None, diffmap_threshold=8, want_diff: bool = False, synthesis: str = "range",
+                            enhancement_threshold: float = 5.0, enhancement_min_hu: float = -400.0):
     """The translation of one NCCT series with both Generators and the HU-range merge, resident on
     the device: what ``_conditioning`` + ``translate_slices`` + ``stored_from_output`` per model and
     ``synthesize`` per slice compute, without a host round trip in between.
@@ -119,9 +121,15 @@ def translate_volume_device(soft_model, lung_model, raw_stored, slopes, intercep
     nmodel: a modules/nmodel U-Net; the difference-map stage then runs between the merge and the
     return: the U-Net over the ``hu`` tensor that is already here, ending in the kernel that adds the
     thresholded uint8 map into ``merged`` (modules/nmodel/inference.py::apply_predicted_diffmap_device),
-    no transfer.  want_diff=True appends the float difference map (device) to the result."""
+    no transfer.  want_diff=True appends the float difference map (device) to the result.
+
+    synthesis="enhancement": the merged tensor is ``synthesize_enhancement`` of the two stored-value
+    series (enhancement_threshold, enhancement_min_hu) instead of the HU-range merge, from one
+    kernel as well; everything else is as above."""
     from .hip import ops
     from .hip import slices as S
+    if synthesis not in ("range", "enhancement"):
+        raise ValueError(f"translate_volume_device: synthesis {synthesis!r} (range or enhancement expected)")
     raw = np.asarray(raw_stored)
     if raw.dtype not in (np.int16, np.uint16):
         raise TypeError(f"translate_volume_device: stored dtype {raw.dtype} (int16 or uint16 expected)")
@@ -160,9 +168,14 @@ def translate_volume_device(soft_model, lung_model, raw_stored, slopes, intercep
                     out = model(x, m)  # concat fused into the stem gather
                 chunks.append(S.resize_aa(out.float(), (H, W)))
             ys.append(torch.cat(chunks).view(D, H, W))
-        so, lo, _, merged = S.translate_merge(bits, slope, inter, ys[0], ys[1], soft_range, lung_range,
-                                              unsigned=unsigned, want_soft=want_stored, want_lung=want_stored,
-                                              want_merged=False, want_f32=True)
+        if synthesis == "enhancement":
+            so, lo, merged = S.translate_enhance(bits, slope, inter, ys[0], ys[1], soft_range, lung_range,
+                                                 enhancement_threshold, enhancement_min_hu, unsigned=unsigned,
+                                                 want_stored=want_stored)
+        else:
+            so, lo, _, merged = S.translate_merge(bits, slope, inter, ys[0], ys[1], soft_range, lung_range,
+                                                  unsigned=unsigned, want_soft=want_stored, want_lung=want_stored,
+                                                  want_merged=False, want_f32=True)
         if nmodel is None:
             return (merged, so, lo) if want_stored else merged
         from .nmodel.inference import apply_predicted_diffmap_device
@@ -186,15 +199,50 @@ def synthesize(raw_stored: np.ndarray, raw_hu: np.ndarray, soft_stored: np.ndarr
     return merged
 
 
+def synthesize_enhancement(raw_stored: np.ndarray, soft_stored: np.ndarray, lung_stored: np.ndarray, slope: float,
+                           intercept: float, threshold: float = 5.0, min_hu: float = -400.0,
+                           soft_rescale: Optional[Tuple[float, float]] = None,
+                           lung_rescale: Optional[Tuple[float, float]] = None) -> np.ndarray:
+    """generate.py:302-477 (synthesis_test, "sCECT v3") for one slice: keep the NCCT stored values
+    and add each model's HU gain over the NCCT, as stored-value units, where that gain exceeds
+    ``threshold`` and the NCCT HU exceeds ``min_hu`` (both strict; soft tissue first, then lung, a
+    voxel can take both).  float32 throughout, one operation per step; the result is float32 and
+    generally not integral.  soft_rescale / lung_rescale: (slope, intercept) of the two translated
+    series when they differ from the NCCT's (the reference reads each file's own pair)."""
+    f = np.float32
+    a, b = f(slope), f(intercept)
+    (sa, sb), (la, lb) = ((a, b) if p is None else (f(p[0]), f(p[1])) for p in (soft_rescale, lung_rescale))
+    m = np.asarray(raw_stored).astype(f)      # astype copies: the input stays untouched
+    hr = m * a + b
+    es = (np.asarray(soft_stored).astype(f) * sa + sb) - hr
+    el = (np.asarray(lung_stored).astype(f) * la + lb) - hr
+    valid = hr > f(min_hu)
+    for e in (es, el):
+        k = (e > f(threshold)) & valid
+        m[k] = m[k] + e[k] / a
+    return m
+
+
 def synthesize_volume(raw_stored, slopes, intercepts, soft_stored, lung_stored, soft_range: Tuple[float, float],
-                      lung_range: Tuple[float, float], device=None, keep_on_device: bool = False):
+                      lung_range: Tuple[float, float], device=None, keep_on_device: bool = False,
+                      mode: str = "range", threshold: float = 5.0, min_hu: float = -400.0):
     """``synthesize`` over a whole series: [D,H,W] stored values (int16 or uint16) of the NCCT
     and the two translations, one rescale slope / intercept per slice -> merged stored values.
     device=None: the per-slice host code.  With a device the merge runs in one kernel there
     (modules/hip/volume.py); keep_on_device=True then returns the merged values as a float32
-    device tensor, the input of ``smooth_volume(..., device=...)``, instead of downloading."""
+    device tensor, the input of ``smooth_volume(..., device=...)``, instead of downloading.
+
+    mode="enhancement": ``synthesize_enhancement`` (threshold, min_hu) in place of ``synthesize``;
+    the result is float32 (a numpy array, or the device tensor with keep_on_device=True) and the
+    two HU ranges are not used."""
+    if mode not in ("range", "enhancement"):
+        raise ValueError(f"synthesize_volume: mode {mode!r} (range or enhancement expected)")
     raw = np.asarray(raw_stored)
     if device is None:
+        if mode == "enhancement":
+            return np.stack([synthesize_enhancement(r, s, g, a, b, threshold, min_hu)
+                             for r, a, b, s, g in zip(raw, slopes, intercepts, np.asarray(soft_stored),
+                                                      np.asarray(lung_stored))])
         return np.stack([synthesize(r, hu_from_stored(r, a, b), s, g, soft_range, lung_range)
                          for r, a, b, s, g in zip(raw, slopes, intercepts, np.asarray(soft_stored),
                                                   np.asarray(lung_stored))])
@@ -205,6 +253,10 @@ def synthesize_volume(raw_stored, slopes, intercepts, soft_stored, lung_stored, 
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=raw.dtype).view(np.int16)).to(dev)
     f32 = lambda v: torch.tensor([float(x) for x in v], dtype=torch.float32)
     with torch.cuda.device(dev):
+        if mode == "enhancement":
+            f = V.merge_enhancement(up(raw), up(soft_stored), up(lung_stored), f32(slopes), f32(intercepts),
+                                    threshold, min_hu, unsigned=raw.dtype == np.uint16)
+            return f if keep_on_device else f.cpu().numpy()
         out, f = V.merge_hu_ranges(up(raw), up(soft_stored), up(lung_stored), f32(slopes), f32(intercepts),
                                    soft_range, lung_range, unsigned=raw.dtype == np.uint16,
                                    want_stored=not keep_on_device, want_f32=keep_on_device)

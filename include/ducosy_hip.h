@@ -642,6 +642,18 @@ int dcs_vol_finish(const void* sm, int sm_dtype, const float* original, int64_t 
 int dcs_vol_merge(const void* raw, const void* soft, const void* lung, int stored_dtype, const float* slope,
                   const float* intercept, int D, int H, int W, float soft_lo, float soft_hi, float lung_lo,
                   float lung_hi, void* out, float* out_f32, void* stream);
+/* Enhancement-difference merge of three stored-value series (the reference's synthesis_test,
+ * generate.py:302-477; modules/inference.py::synthesize_enhancement on every slice).  Per voxel,
+ * with a = slope[z], b = intercept[z], in float32, one IEEE operation per step (no fused
+ * multiply-add, the division correctly rounded):
+ *   r  = f32(raw);  hr = r*a + b;  hs = f32(soft)*a + b;  hl = f32(lung)*a + b
+ *   es = hs - hr;   el = hl - hr;  valid = hr > min_hu
+ *   m  = r;  if (es > threshold && valid) m = m + es / a;  if (el > threshold && valid) m = m + el / a
+ * Both comparisons are strict; a voxel can take both additions, soft tissue first.  out_f32 = m
+ * (float32, generally not integral).  stored_dtype: DCS_VOL_I16 or DCS_VOL_U16. */
+int dcs_vol_merge_enhance(const void* raw, const void* soft, const void* lung, int stored_dtype, const float* slope,
+                          const float* intercept, int D, int H, int W, float threshold, float min_hu,
+                          float* out_f32, void* stream);
 
 /* ---- slice series of the resident inference path (generate.py --pipeline resident:
  *      modules/inference.py::stored_from_output + synthesize, torchvision Resize) ---- */
@@ -664,6 +676,18 @@ int dcs_vol_translate_merge(const void* raw, int stored_dtype, const float* slop
                             const float* y_soft, const float* y_lung, int D, int H, int W, float soft_lo,
                             float soft_hi, float soft_span, float lung_lo, float lung_hi, float lung_span,
                             void* soft_stored, void* lung_stored, void* merged, float* merged_f32, void* stream);
+/* Model outputs -> stored values -> enhancement-difference merge in one pass.  ps and pl are
+ * dcs_vol_translate_merge's stored values of the two outputs (same operations, same truncating
+ * cast); then dcs_vol_merge_enhance's rule per voxel with a = slope[z], b = intercept[z]:
+ *   r  = f32(raw);  hr = r*a + b;  hs = f32(ps)*a + b;  hl = f32(pl)*a + b
+ *   es = hs - hr;   el = hl - hr;  valid = hr > min_hu
+ *   m  = r;  if (es > threshold && valid) m = m + es / a;  if (el > threshold && valid) m = m + el / a
+ * so merged_f32 equals dcs_vol_merge_enhance of the stored series bit for bit.  merged_f32 is
+ * required; soft_stored and lung_stored (stored dtype) are optional. */
+int dcs_vol_translate_enhance(const void* raw, int stored_dtype, const float* slope, const float* intercept,
+                              const float* y_soft, const float* y_lung, int D, int H, int W, float soft_lo,
+                              float soft_span, float lung_lo, float lung_span, float threshold, float min_hu,
+                              void* soft_stored, void* lung_stored, float* merged_f32, void* stream);
 /* Antialiased bilinear resize (F.interpolate(mode="bilinear", align_corners=False, antialias=True))
  * of NC planes [H][W] -> [oh][ow], separable: horizontal pass, then vertical pass.  The caller
  * builds the weights (modules/hip/slices.py::aa_tables) and passes them as DEVICE tables, one set

@@ -20,7 +20,9 @@ staged path's ATen resizes differ from the resize kernel in the last bits otherw
 truncating cast can turn into off-by-one stored values).  Prints ``identical: true/false`` and one
 JSON line.  --apply_diffmap adds a third leg, the resident path with the difference-map stage
 (a seeded UNet3DLight base 16, or --nmodel full32 for UNet3D base 32; modules/nmodel), and reports it
-as ``resident_diffmap_s`` next to ``resident_s``.
+as ``resident_diffmap_s`` next to ``resident_s``.  --synthesis enhancement runs every leg with the
+enhancement-difference merge (sCECT v3) in place of the HU-range merge and adds ``translate_enhance``
+to the kernel table, beside ``translate_merge``.
 """
 import argparse
 import json
@@ -44,7 +46,7 @@ from modules.model import Generator  # noqa: E402
 SOFT, LUNG = (-150, 250), (-1000, -150)
 
 
-def staged(models, raw, slopes, inters, img_size, batch, dev):
+def staged(models, raw, slopes, inters, img_size, batch, dev, mode="range"):
     hu = [hu_from_stored(r, a, b) for r, a, b in zip(raw, slopes, inters)]
     stored = []
     for kind, model, (lo, hi) in (("soft_tissue", models[0], SOFT), ("lung", models[1], LUNG)):
@@ -52,13 +54,14 @@ def staged(models, raw, slopes, inters, img_size, batch, dev):
                               _conditioning(model, kind, hu, dev))
         stored.append(np.stack([stored_from_output(y, lo, hi, a, b, raw.dtype)
                                 for y, a, b in zip(ys, slopes, inters)]))
-    on_dev = synthesize_volume(raw, slopes, inters, stored[0], stored[1], SOFT, LUNG, device=dev, keep_on_device=True)
+    on_dev = synthesize_volume(raw, slopes, inters, stored[0], stored[1], SOFT, LUNG, device=dev, keep_on_device=True,
+                               mode=mode)
     return smooth_volume(on_dev, device=dev)
 
 
-def resident(models, raw, slopes, inters, img_size, batch, dev, nmodel=None):
+def resident(models, raw, slopes, inters, img_size, batch, dev, nmodel=None, mode="range"):
     merged = translate_volume_device(models[0], models[1], raw, slopes, inters, SOFT, LUNG, img_size, batch, dev,
-                                     nmodel=nmodel)
+                                     nmodel=nmodel, synthesis=mode)
     return smooth_volume_device(merged).cpu().numpy()
 
 
@@ -102,9 +105,9 @@ def generators_only(models, D, img_size, batch, dev):
     return _wall(run)[0]
 
 
-def kernel_times(raw, slopes, inters, dev, reps):
+def kernel_times(raw, slopes, inters, dev, reps, mode="range"):
     """Event time and achieved GB/s (algorithmic bytes: inputs read once, outputs written once) of the
-    three slices.hip kernels at the benchmark's series shape."""
+    slices.hip kernels at the benchmark's series shape; mode "enhancement" adds translate_enhance."""
     D, H, W = raw.shape
     n = D * H * W
     res = {}
@@ -118,6 +121,11 @@ def kernel_times(raw, slopes, inters, dev, reps):
     ms = _event_ms(lambda: S.translate_merge(bits, a, b, ys, yl, SOFT, LUNG, want_soft=True, want_lung=True,
                                              want_merged=True), reps)
     res["translate_merge_all_outputs"] = {"ms": round(ms, 4), "GBps": round(20 * n / ms / 1e6, 1)}
+    if mode == "enhancement":
+        ms = _event_ms(lambda: S.translate_enhance(bits, a, b, ys, yl, SOFT, LUNG), reps)
+        res["translate_enhance_f32_only"] = {"ms": round(ms, 4), "GBps": round(14 * n / ms / 1e6, 1)}
+        ms = _event_ms(lambda: S.translate_enhance(bits, a, b, ys, yl, SOFT, LUNG, want_stored=True), reps)
+        res["translate_enhance_with_stored"] = {"ms": round(ms, 4), "GBps": round(18 * n / ms / 1e6, 1)}
     x = ys[:, None]
     hh, hw = max(1, H // 2), max(1, W // 2)
     small = S.resize_aa(x, (hh, hw))
@@ -141,6 +149,8 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--apply_diffmap", action="store_true", help="also time the resident path with the difference-map stage")
     ap.add_argument("--nmodel", choices=["light16", "full32"], default="light16")
+    ap.add_argument("--synthesis", choices=["range", "enhancement"], default="range",
+                    help="the merge both legs run: the HU-range merge or the enhancement-difference merge")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_generate.py needs a GPU")
@@ -150,11 +160,12 @@ def main():
     raw, slopes, inters = phantom.ct_batch(0, a.slices, a.size)
     torch.manual_seed(0)
     models = (Generator(3, 9).to(dev).eval(), Generator(2, 9).to(dev).eval())
-    legs = {"staged": staged, "resident": resident}
+    legs = {"staged": lambda *args: staged(*args, mode=a.synthesis),
+            "resident": lambda *args: resident(*args, mode=a.synthesis)}
     if a.apply_diffmap:
         from modules.nmodel import UNet3D, UNet3DLight
         nmodel = (UNet3DLight(base_channels=16) if a.nmodel == "light16" else UNet3D(base_channels=32)).to(dev).eval()
-        legs["resident_diffmap"] = lambda *args: resident(*args, nmodel=nmodel)
+        legs["resident_diffmap"] = lambda *args: resident(*args, nmodel=nmodel, mode=a.synthesis)
     times = {k: [] for k in legs}
     outs = {}
     for rep in range(a.reps + 1):            # rep 0 is the warm-up of both legs at the full shape
@@ -165,9 +176,11 @@ def main():
             outs[name] = out
     res = {"metric": "generate_patient_seconds", "device": torch.cuda.get_device_name(dev),
            "shape": f"{a.slices}x{a.size}x{a.size}", "img_size": img_size, "slice_batch": a.slice_batch,
+           "synthesis": a.synthesis,
            "staged_s": round(min(times["staged"]), 4), "resident_s": round(min(times["resident"]), 4),
            "staged_all_s": [round(t, 4) for t in times["staged"]],
            "resident_all_s": [round(t, 4) for t in times["resident"]]}
+    res["resident_median_s"] = round(float(np.median(times["resident"])), 4)
     res["staged_over_resident"] = round(res["staged_s"] / res["resident_s"], 3)
     if a.apply_diffmap:
         res["nmodel"] = a.nmodel
@@ -181,7 +194,7 @@ def main():
         res["differing_share"], res["largest_difference"] = float((d != 0).mean()), int(d.max())
     res["generators_only_s"] = round(min(generators_only(models, a.slices, img_size, a.slice_batch, dev)
                                          for _ in range(a.reps)), 4)
-    res["kernels"] = kernel_times(raw, slopes, inters, dev, a.reps)
+    res["kernels"] = kernel_times(raw, slopes, inters, dev, a.reps, a.synthesis)
     print("identical:", "true" if same else "false")
     print(json.dumps(res))
     if img_size == a.size and not same:
