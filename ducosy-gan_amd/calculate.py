@@ -28,6 +28,15 @@ Differences from the reference, all deliberate:
     (modules/lpips_weights.py); parity with the reference's own numbers is unpinned.  Without the
     flag its column is empty, as the reference leaves it without the library, and so it is for
     slices below 31 x 31; the box and scatter plots need seaborn and are skipped;
+  * --regions (off by default; the files above are the same with and without it) adds a region-wise
+    evaluation of this package's own, which the reference does not have, on either --device: MAE, bias,
+    PSNR and SSIM per owner of the dual-range synthesis (lung, soft tissue, rest: the NCCT HU ranges
+    of generate.py, --lung_hu_min ... --soft_hu_max) and over the truly enhancing voxels
+    (--enhancement_threshold, --enhancement_min_hu), with the Dice overlap of the predicted and the
+    true enhancement (modules/metrics.py::REGIONS).  It needs a VUE series and writes
+    ``regions/{dataset}_{patient}_regions.csv``, ``result_region_metrics.pkl`` and
+    ``summary_statistics_regions.csv``; an empty region is an empty cell.  --mask composes with it;
+    regions from anatomical masks or organ labels are out of scope;
   * nothing happens at import or while parsing arguments: no environment variable is set and no
     directory is created before the conversion starts.
 DICOM files are read with modules/dicom.py.
@@ -82,6 +91,18 @@ def get_args(argv=None):
                    help="Compute LPIPS (AlexNet) of STD against Generated (slices of at least 31 x 31), on either "
                         "--device, with the weights in these torch.save'd state dicts: lpips.LPIPS(net='alex')'s, "
                         "or torchvision's alexnet and the lpips package's alex.pth")
+    p.add_argument("--regions", action="store_true",
+                   help="Also write region-wise metrics (per HU-range owner of the synthesis: lung, soft, rest; and over "
+                        "the truly enhancing voxels) of every patient with a VUE series, on either --device, to files "
+                        "of their own")
+    p.add_argument("--soft_hu_min", type=int, default=-150, help="--regions: the soft-tissue model's HU range")
+    p.add_argument("--soft_hu_max", type=int, default=250)
+    p.add_argument("--lung_hu_min", type=int, default=-1000, help="--regions: the lung model's HU range")
+    p.add_argument("--lung_hu_max", type=int, default=-150)
+    p.add_argument("--enhancement_threshold", type=float, default=5.0,
+                   help="--regions: a voxel enhances where CECT - NCCT exceeds this many HU")
+    p.add_argument("--enhancement_min_hu", type=float, default=-400.0,
+                   help="--regions: and only where the NCCT HU exceeds this")
     return p.parse_args(argv)
 
 
@@ -157,14 +178,54 @@ def convert(args):
     return out_dir, data_dir, tasks
 
 
-def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=False, lpips_weights=None):
-    """Metrics of one patient and its detail CSV; None when the STD or generated stack is missing."""
+class RegionRun:
+    """--regions: the HU ranges, the directory of the per-patient CSVs and the aggregates so far."""
+
+    def __init__(self, args, out_dir):
+        self.spec = M.RegionSpec(args.lung_hu_min, args.lung_hu_max, args.soft_hu_min, args.soft_hu_max,
+                                 args.enhancement_threshold, args.enhancement_min_hu)
+        self.dir = os.path.join(out_dir, "regions")
+        self.result_path = os.path.join(out_dir, "result_region_metrics.pkl")
+        self.summary = {"patient": [], **{k: [] for k in M.REGION_COLUMNS}}
+
+
+def process_regions(dataset, patient, run, device, std, gen, vue):
+    """Region metrics of one patient (series as arrays, or already on the device) and its CSV."""
+    if vue is None:
+        print(f"  {dataset} {patient}: no VUE series, skipped for regions")
+        return
+    try:
+        if device is None:
+            agg, per_slice = M.region_metrics(std, gen, vue, run.spec)
+        else:
+            from modules import metrics_gpu
+            agg, per_slice = metrics_gpu.region_metrics(std, gen, vue, device=device, spec=run.spec)
+        os.makedirs(run.dir, exist_ok=True)
+        M.write_region_csv(os.path.join(run.dir, f"{dataset}_{patient}_regions.csv"), per_slice)
+        run.summary["patient"].append(f"{dataset}_{patient}")
+        for k in M.REGION_COLUMNS:
+            run.summary[k].append(agg[k])
+    except Exception as e:
+        print(f"Error in the region metrics of {patient}: {e}")
+        traceback.print_exc()
+
+
+def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=False, lpips_weights=None, regions=None,
+                    metrics=True):
+    """Metrics of one patient and its detail CSV; None when the STD or generated stack is missing.
+    regions: a RegionRun, for the region metrics as well (metrics=False: for those alone)."""
     path = lambda c: os.path.join(data_dir, f"{dataset}_{patient}_{c}.npy")
     if not (os.path.exists(path("std")) and os.path.exists(path("generated"))):
         return None
     try:
         std, gen = np.load(path("std")), np.load(path("generated"))
         vue = np.load(path("vue")) if os.path.exists(path("vue")) else None
+        if regions is not None and device is not None:   # one upload serves both calls
+            from modules import metrics_gpu
+            std, gen, vue = (None if v is None else metrics_gpu.to_device(v, device) for v in (std, gen, vue))
+        if not metrics:
+            process_regions(dataset, patient, regions, device, std, gen, vue)
+            return None
         if device is None:
             patient_metrics, csv_data = M.evaluate_patient(std, gen, vue, ms_ssim, lpips_weights)
         else:
@@ -175,6 +236,8 @@ def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=Fals
             M.write_detail_csv(os.path.join(detail_dir, f"{dataset}_{patient}_metrics.csv"), csv_data, vue is not None)
         except Exception as e:
             print(f"Error saving CSV for {patient}: {e}")
+        if regions is not None:
+            process_regions(dataset, patient, regions, device, std, gen, vue)
         return patient_metrics
     except Exception as e:
         print(f"Error processing {patient}: {e}")
@@ -182,7 +245,7 @@ def process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim=Fals
         return None
 
 
-def calculate(out_dir, data_dir, tasks, device, ms_ssim=False, lpips_weights=None):
+def calculate(out_dir, data_dir, tasks, device, ms_ssim=False, lpips_weights=None, regions=None):
     print(f"\nCalculating metrics for generated images (device: {device or 'cpu'})...")
     result_path = os.path.join(out_dir, "result_all_metrics.pkl")
     detail_dir = os.path.join(out_dir, "detail")
@@ -194,11 +257,14 @@ def calculate(out_dir, data_dir, tasks, device, ms_ssim=False, lpips_weights=Non
         drop = {i for i, v in enumerate(summary["mae"]) if len(v) > 1 and v[1] == 0.0}
         summary = {k: [v for i, v in enumerate(vals) if i not in drop] for k, vals in summary.items()}
         print(f"Existing results found at {result_path}. Loaded previous calculations.")
+        if regions is not None and not os.path.exists(regions.result_path):
+            for dataset, patient in tasks:
+                process_patient(dataset, patient, data_dir, detail_dir, device, regions=regions, metrics=False)
     else:
         summary = {k: [] for k in M.METRICS}
         valid = 0
         for n, (dataset, patient) in enumerate(tasks, 1):
-            res = process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim, lpips_weights)
+            res = process_patient(dataset, patient, data_dir, detail_dir, device, ms_ssim, lpips_weights, regions)
             print(f"  [{n}/{len(tasks)}] {dataset} {patient}: {'done' if res is not None else 'skipped'}")
             if res is None:
                 continue
@@ -211,6 +277,10 @@ def calculate(out_dir, data_dir, tasks, device, ms_ssim=False, lpips_weights=Non
         with open(result_path, "wb") as f:
             pickle.dump(summary, f)
         print(f"Calculations complete. Valid patients: {valid}. Results saved to {result_path}")
+    if regions is not None and regions.summary["patient"]:
+        with open(regions.result_path, "wb") as f:
+            pickle.dump(regions.summary, f)
+        print(f"Region metrics of {len(regions.summary['patient'])} patients saved to {regions.result_path}")
     try:
         print("\n[Global Average: CECT(STD) vs Generated]")
         for name, key in (("MAE ", "mae"), ("PSNR", "psnr"), ("SSIM", "ssim")):
@@ -220,10 +290,11 @@ def calculate(out_dir, data_dir, tasks, device, ms_ssim=False, lpips_weights=Non
     print("Plots skipped: the reference draws them with seaborn, which is not installed.")
 
 
-def summary_statistics(detail_dir, summary_csv_path):
-    """Mean, std, min, max, median and count of every detail-CSV column over all patients."""
+def summary_statistics(detail_dir, summary_csv_path, pattern="*_metrics.csv"):
+    """Mean, std, min, max, median and count of every column of the CSVs ``pattern`` names in
+    detail_dir (the detail CSVs by default) over all patients."""
     print(f"\nComputing summary statistics from {detail_dir}...")
-    files = sorted(glob.glob(os.path.join(detail_dir, "*_metrics.csv"))) if os.path.exists(detail_dir) else []
+    files = sorted(glob.glob(os.path.join(detail_dir, pattern))) if os.path.exists(detail_dir) else []
     if not files:
         print("No CSV files found in detail result directory.")
         return
@@ -266,12 +337,15 @@ def main(argv=None):
         from modules import lpips_weights as LW
         lpips_weights = LW.load(args.lpips_weights)
     out_dir, data_dir, tasks = convert(args)
+    regions = RegionRun(args, out_dir) if args.regions else None
     if tasks:
-        calculate(out_dir, data_dir, tasks, device, args.ms_ssim, lpips_weights)
+        calculate(out_dir, data_dir, tasks, device, args.ms_ssim, lpips_weights, regions)
     else:
         print("No tasks found. Please check input directories and arguments.")
     summary_statistics(os.path.join(out_dir, "detail"),
                        os.path.join(out_dir, "summary_statistics_masked.csv" if args.mask else "summary_statistics.csv"))
+    if regions is not None:
+        summary_statistics(regions.dir, os.path.join(out_dir, "summary_statistics_regions.csv"), "*_regions.csv")
 
 
 if __name__ == "__main__":

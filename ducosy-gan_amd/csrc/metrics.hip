@@ -2,8 +2,9 @@
 // similarity and the min/max of a volume pair from one pass, per-slice SSIM, the Sobel texture
 // similarity, the per-slice normalised Euclidean distance and the L1 distance of two row-sorted
 // volumes (the Wasserstein-1 distance of EMD), and the levels of MS-SSIM (the per-slice sums of one
-// level and the 2x2 pooling between levels).  Dense float32 [D][H][W] volumes, x fastest; every
-// result is float64 per slice.
+// level and the 2x2 pooling between levels), and the region-wise sums of calculate.py --regions
+// (per HU-range owner and over the true enhancement: counts, error sums, the SSIM map).  Dense
+// float32 [D][H][W] volumes, x fastest; every result is float64 per slice.
 //
 // Arithmetic (the spec modules/metrics.py follows too): the reference's numpy elementwise
 // expressions stay in float32, one IEEE operation per step (a - b, its square, the (x - off) / div
@@ -145,8 +146,8 @@ __global__ void __launch_bounds__(MT) pair_kernel(const float* __restrict__ a, c
     if (threadIdx.x == 0) out[0] = s0;
 }
 
-// out[z][k] = the partials ws[z][0..P)[k] combined in index order; ops holds two bits per k
-__global__ void __launch_bounds__(MT) fold_kernel(const double* __restrict__ ws, int D, int P, int K, unsigned ops,
+// out[z][k] = the partials ws[z][0..P)[k] combined in index order; ops holds two bits per k (K <= 32)
+__global__ void __launch_bounds__(MT) fold_kernel(const double* __restrict__ ws, int D, int P, int K, uint64_t ops,
                                                   double* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * MT + threadIdx.x;
     if (i >= (int64_t)D * K) return;
@@ -162,26 +163,20 @@ __global__ void __launch_bounds__(MT) fold_kernel(const double* __restrict__ ws,
     out[i] = v;
 }
 
-// Sum of the SSIM map over one TX x TY tile of the interior (H-6) x (W-6) of slice z.  The
-// interior's 7x7 windows lie inside the image, so the 'reflect' border of the filters is never
-// read.  The tile and its 6-pixel halo are staged in LDS after the affine map; a thread owns one
-// column of a strip of SR rows, walks down SR + 6 input rows, forms the five horizontal 7-sums of
-// each once and keeps the last seven in registers (the column sums are reused by seven outputs).
+// The SSIM map of one TX x TY tile of the interior (H-6) x (W-6) of a slice.  The interior's 7x7
+// windows lie inside the image, so the 'reflect' border of the filters is never read.  The tile
+// and its 6-pixel halo are staged in LDS (ssim_stage); a thread owns one column of a strip of SR
+// rows, walks down SR + 6 input rows, forms the five horizontal 7-sums of each once and keeps the
+// last seven in registers (the column sums are reused by seven outputs), and hands every map value
+// of its column to emit(row in the strip, value).
 // With N = 49 and the window sums sx, sy, sxx, syy, sxy (float64) the factors N^2 cancel in
 //   S = ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),  v = N/(N-1) (u.. - u.u.):
 //   S = ((2 sx sy + c1)((N sxy - sx sy) 49/24 + c2)) / ((sx^2 + sy^2 + c1)((N (sxx + syy) - sx^2 - sy^2) 49/48 + c2))
 // with c1 = C1 N^2, c2 = C2 N^2: one division per pixel, and exact on integer-valued data.
-__global__ void __launch_bounds__(MT) ssim_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
-                                                  int ntx, int nty, Aff ta, Aff tb, double c1, double c2,
-                                                  double* __restrict__ ws) {
-    __shared__ float sa[TY + 6][TX + 6], sb[TY + 6][TX + 6];
-    __shared__ double red[MT / WAVE];
-    const unsigned ntile = (unsigned)(ntx * nty);
-    const int64_t z = blockIdx.x / ntile;
-    const int tile = (int)(blockIdx.x % ntile);
-    const int tx0 = (tile % ntx) * TX, ty0 = (tile / ntx) * TY;
-    const float* __restrict__ pa = a + z * H * W;
-    const float* __restrict__ pb = b + z * H * W;
+// ssim_kernel sums the map over the tile, region_ssim_kernel per region: both read this map.
+using SsimTile = float[TY + 6][TX + 6];
+__device__ __forceinline__ void ssim_stage(const float* __restrict__ pa, const float* __restrict__ pb, int H, int W,
+                                           int tx0, int ty0, const Aff& ta, const Aff& tb, SsimTile& sa, SsimTile& sb) {
     for (int i = threadIdx.x; i < (TY + 6) * (TX + 6); i += MT) {
         const int r = i / (TX + 6), c = i % (TX + 6);
         const int y = ty0 + r, x = tx0 + c;
@@ -193,46 +188,219 @@ __global__ void __launch_bounds__(MT) ssim_kernel(const float* __restrict__ a, c
         sa[r][c] = va;
         sb[r][c] = vb;
     }
+}
+template <class Emit>
+__device__ __forceinline__ void ssim_strip(const SsimTile& sa, const SsimTile& sb, int r0, int cx, double c1, double c2,
+                                           Emit&& emit) {
+    double ring[7][5];
+#pragma unroll
+    for (int i = 0; i < SR + 6; ++i) {
+        double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const double x = (double)sa[r0 + i][cx + k], y = (double)sb[r0 + i][cx + k];
+            m0 += x;
+            m1 += y;
+            m2 += x * x;
+            m3 += y * y;
+            m4 += x * y;
+        }
+        ring[i % 7][0] = m0, ring[i % 7][1] = m1, ring[i % 7][2] = m2, ring[i % 7][3] = m3, ring[i % 7][4] = m4;
+        if (i >= 6) {
+            double s[5];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                s[q] = ring[(i - 6) % 7][q];
+#pragma unroll
+                for (int j = i - 5; j <= i; ++j) s[q] += ring[j % 7][q];
+            }
+            const double sxsy = s[0] * s[1], sx2 = s[0] * s[0], sy2 = s[1] * s[1];
+            const double A1 = 2.0 * sxsy + c1;
+            const double A2 = (49.0 * s[4] - sxsy) * (49.0 / 24.0) + c2;
+            const double B1 = sx2 + sy2 + c1;
+            const double B2 = (49.0 * (s[2] + s[3]) - sx2 - sy2) * (49.0 / 48.0) + c2;
+            emit(i - 6, (A1 * A2) / (B1 * B2));
+        }
+    }
+}
+
+// Sum of the SSIM map over one tile of the interior of slice z.
+__global__ void __launch_bounds__(MT) ssim_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
+                                                  int ntx, int nty, Aff ta, Aff tb, double c1, double c2,
+                                                  double* __restrict__ ws) {
+    __shared__ SsimTile sa, sb;
+    __shared__ double red[MT / WAVE];
+    const unsigned ntile = (unsigned)(ntx * nty);
+    const int64_t z = blockIdx.x / ntile;
+    const int tile = (int)(blockIdx.x % ntile);
+    const int tx0 = (tile % ntx) * TX, ty0 = (tile / ntx) * TY;
+    ssim_stage(a + z * H * W, b + z * H * W, H, W, tx0, ty0, ta, tb, sa, sb);
     __syncthreads();
     const int Ho = H - 6, Wo = W - 6;
     const int cx = threadIdx.x & (TX - 1), r0 = (int)(threadIdx.x / TX) * SR;
     const bool col_ok = tx0 + cx < Wo;
     double acc = 0.0;
-    if (ty0 + r0 < Ho) {  // wave-uniform: a strip is one wave
-        double ring[7][5];
+    if (ty0 + r0 < Ho)  // wave-uniform: a strip is one wave
+        ssim_strip(sa, sb, r0, cx, c1, c2, [&](int j, double v) {
+            if (col_ok && ty0 + r0 + j < Ho) acc += v;
+        });
+    acc = block_red<OP_ADD>(acc, red);
+    if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+}
+
+// Region-wise evaluation (calculate.py --regions; modules/metrics.py::region_sums states it).  A
+// voxel's owner follows synthesis(): lung where lung_min <= vue <= lung_max, else soft where
+// soft_min <= vue <= soft_max, else rest; over these lies the true enhancement (std - vue) > thr
+// and vue > min_hu, and the predicted one with gen in place of std.  float32 comparisons on
+// float32 differences, as synthesize_enhancement takes them.
+constexpr int NREG = 4, NRS = DCS_MET_REGION_NSUMS, NRSS = DCS_MET_REGION_NSSIM;
+enum { RG_LUNG = 0, RG_SOFT = 1, RG_REST = 2, RG_ENH = 3, RG_ENH_BIT = 4 };  // map byte: owner | RG_ENH_BIT
+static_assert(NRS == 4 * NREG + 5 && NRSS == 2 * NREG && NRS <= MT && NRS <= 32, "one thread and two fold bits per column");
+struct RegionRanges {
+    float lung_min, lung_max, soft_min, soft_max, thr, min_hu;
+};
+
+// the N sums of a block in a fixed order: lanes by shuffles, then the four waves through LDS;
+// thread k < N writes out[k]
+template <int N>
+__device__ __forceinline__ void block_sum_n(double (&v)[N], double (*red)[MT / WAVE], double* __restrict__ out) {
 #pragma unroll
-        for (int i = 0; i < SR + 6; ++i) {
-            double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0;
+    for (int k = 0; k < N; ++k) {
 #pragma unroll
-            for (int k = 0; k < 7; ++k) {
-                const double x = (double)sa[r0 + i][cx + k], y = (double)sb[r0 + i][cx + k];
-                m0 += x;
-                m1 += y;
-                m2 += x * x;
-                m3 += y * y;
-                m4 += x * y;
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const double* r = red[threadIdx.x];
+        out[threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
+    }
+}
+
+// One pass over chunk p of slice z of the three series, 12 bytes per voxel.  Writes the block's
+// record of NRS sums: per region n, sum|std-gen|, sum f32((std-gen)^2), sum (gen-std), then TP,
+// FP, FN of the predicted against the true enhancement and sum (std-vue), sum (gen-vue) over the
+// true one; and, if asked, one byte per voxel (owner | RG_ENH_BIT) for region_ssim_kernel.
+template <int VEC>
+__global__ void __launch_bounds__(MT) region_kernel(const float* __restrict__ vue, const float* __restrict__ std_,
+                                                    const float* __restrict__ gen, int64_t S, int P, RegionRanges rr,
+                                                    unsigned char* __restrict__ map, double* __restrict__ ws) {
+    __shared__ double red[NRS][MT / WAVE];
+    const int64_t z = blockIdx.x / (unsigned)P;
+    const int p = (int)(blockIdx.x % (unsigned)P);
+    const float* __restrict__ pv = vue + z * S;
+    const float* __restrict__ ps = std_ + z * S;
+    const float* __restrict__ pg = gen + z * S;
+    unsigned char* __restrict__ pm = map ? map + z * S : nullptr;  // kernel argument: wave-uniform
+    const int64_t start = (int64_t)p * PCH;
+    const int64_t end = start + PCH < S ? start + PCH : S;
+    int cnt[NREG] = {0, 0, 0, 0}, tp = 0, fp = 0, fn = 0;
+    double sab[NREG] = {0.0, 0.0, 0.0, 0.0}, ssq[NREG] = {0.0, 0.0, 0.0, 0.0}, sbi[NREG] = {0.0, 0.0, 0.0, 0.0};
+    double set = 0.0, sep = 0.0;
+    using VF = float __attribute__((ext_vector_type(VEC)));
+    using VB = unsigned char __attribute__((ext_vector_type(VEC)));
+#pragma unroll 1
+    for (int64_t i = start + (int64_t)threadIdx.x * VEC; i < end; i += MT * VEC) {  // S % VEC == 0
+        float vv[VEC], vs[VEC], vg[VEC];
+        unsigned char mb[VEC];
+        if (VEC == 1) {
+            vv[0] = pv[i];
+            vs[0] = ps[i];
+            vg[0] = pg[i];
+        } else {
+            const VF qv = *reinterpret_cast<const VF*>(pv + i);
+            const VF qs = *reinterpret_cast<const VF*>(ps + i);
+            const VF qg = *reinterpret_cast<const VF*>(pg + i);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                vv[v] = qv[v];
+                vs[v] = qs[v];
+                vg[v] = qg[v];
             }
-            ring[i % 7][0] = m0, ring[i % 7][1] = m1, ring[i % 7][2] = m2, ring[i % 7][3] = m3, ring[i % 7][4] = m4;
-            if (i >= 6) {
-                double s[5];
+        }
 #pragma unroll
-                for (int q = 0; q < 5; ++q) {
-                    s[q] = ring[(i - 6) % 7][q];
+        for (int v = 0; v < VEC; ++v) {
+            const float x = vv[v], s = vs[v], g = vg[v];
+            const float d = s - g, q = d * d, b = g - s;
+            const float et = s - x, ep = g - x;
+            const bool lung = x >= rr.lung_min && x <= rr.lung_max;
+            const bool soft = !lung && x >= rr.soft_min && x <= rr.soft_max;
+            const int own = lung ? RG_LUNG : (soft ? RG_SOFT : RG_REST);
+            const bool valid = x > rr.min_hu;
+            const bool te = et > rr.thr && valid, pe = ep > rr.thr && valid;
+            mb[v] = (unsigned char)(own | (te ? RG_ENH_BIT : 0));
+            const double da = (double)fabsf(d), dq = (double)q, db = (double)b;
 #pragma unroll
-                    for (int j = i - 5; j <= i; ++j) s[q] += ring[j % 7][q];
-                }
-                const double sxsy = s[0] * s[1], sx2 = s[0] * s[0], sy2 = s[1] * s[1];
-                const double A1 = 2.0 * sxsy + c1;
-                const double A2 = (49.0 * s[4] - sxsy) * (49.0 / 24.0) + c2;
-                const double B1 = sx2 + sy2 + c1;
-                const double B2 = (49.0 * (s[2] + s[3]) - sx2 - sy2) * (49.0 / 48.0) + c2;
-                const double v = (A1 * A2) / (B1 * B2);
-                if (col_ok && ty0 + r0 + i - 6 < Ho) acc += v;
+            for (int r = 0; r < NREG; ++r) {
+                const bool in = r == RG_ENH ? te : own == r;
+                cnt[r] += in ? 1 : 0;
+                sab[r] += in ? da : 0.0;
+                ssq[r] += in ? dq : 0.0;
+                sbi[r] += in ? db : 0.0;
+            }
+            tp += (te && pe) ? 1 : 0;
+            fp += (!te && pe) ? 1 : 0;
+            fn += (te && !pe) ? 1 : 0;
+            set += te ? (double)et : 0.0;
+            sep += te ? (double)ep : 0.0;
+        }
+        if (pm) {
+            if (VEC == 1) {
+                pm[i] = mb[0];
+            } else {
+                VB qm;
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) qm[v] = mb[v];
+                *reinterpret_cast<VB*>(pm + i) = qm;
             }
         }
     }
-    acc = block_red<OP_ADD>(acc, red);
-    if (threadIdx.x == 0) ws[blockIdx.x] = acc;
+    double rec[NRS];  // a thread counts at most PCH / MT voxels: exact in int and in double
+#pragma unroll
+    for (int r = 0; r < NREG; ++r) rec[4 * r] = (double)cnt[r], rec[4 * r + 1] = sab[r], rec[4 * r + 2] = ssq[r], rec[4 * r + 3] = sbi[r];
+    rec[16] = (double)tp, rec[17] = (double)fp, rec[18] = (double)fn, rec[19] = set, rec[20] = sep;
+    block_sum_n<NRS>(rec, red, ws + (int64_t)blockIdx.x * NRS);
+}
+
+// The SSIM map of (std, gen) over one tile of the interior of slice z, as ssim_kernel forms it,
+// summed per region: the block's record is {count, sum} of lung, soft, rest and the true
+// enhancement.  A pixel's regions come from the byte region_kernel wrote for it (1 byte read per
+// output pixel; no halo: only the outputs are classified).
+__global__ void __launch_bounds__(MT) region_ssim_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                         const unsigned char* __restrict__ map, int H, int W, int ntx,
+                                                         int nty, double c1, double c2, double* __restrict__ ws) {
+    __shared__ SsimTile sa, sb;
+    __shared__ double red[NRSS][MT / WAVE];
+    const unsigned ntile = (unsigned)(ntx * nty);
+    const int64_t z = blockIdx.x / ntile;
+    const int tile = (int)(blockIdx.x % ntile);
+    const int tx0 = (tile % ntx) * TX, ty0 = (tile / ntx) * TY;
+    const int Ho = H - 6, Wo = W - 6;
+    const int cx = threadIdx.x & (TX - 1), r0 = (int)(threadIdx.x / TX) * SR;
+    const bool col_ok = tx0 + cx < Wo;
+    // output (y, x) of the interior is pixel (y + 3, x + 3) of the slice
+    const unsigned char* __restrict__ pm = map + z * H * W + (int64_t)(ty0 + r0 + 3) * W + (tx0 + cx + 3);
+    unsigned char mb[SR];
+#pragma unroll
+    for (int j = 0; j < SR; ++j) mb[j] = (col_ok && ty0 + r0 + j < Ho) ? pm[(int64_t)j * W] : (unsigned char)0xff;
+    Aff id;
+    id.off = 0.f, id.div = 1.f, id.ident = 1;
+    ssim_stage(a + z * H * W, b + z * H * W, H, W, tx0, ty0, id, id, sa, sb);
+    __syncthreads();
+    double rec[NRSS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (ty0 + r0 < Ho)  // wave-uniform: a strip is one wave
+        ssim_strip(sa, sb, r0, cx, c1, c2, [&](int j, double v) {
+            const int m = mb[j];  // 0xff outside the interior: no owner, and skipped
+            if (m != 0xff) {
+#pragma unroll
+                for (int r = 0; r < NREG; ++r) {
+                    const bool in = r == RG_ENH ? (m & RG_ENH_BIT) != 0 : (m & 3) == r;
+                    rec[2 * r] += in ? 1.0 : 0.0;
+                    rec[2 * r + 1] += in ? v : 0.0;
+                }
+            }
+        });
+    block_sum_n<NRSS>(rec, red, ws + (int64_t)blockIdx.x * NRSS);
 }
 
 // skimage.filters.sobel of both slices on the fly over one TX x TY tile, 'reflect' border:
@@ -445,7 +613,7 @@ static bool aff_ok(const float* affine) {
     return true;
 }
 
-static int fold(const double* ws, int D, int P, int K, unsigned ops, double* out, hipStream_t s, const char* what) {
+static int fold(const double* ws, int D, int P, int K, uint64_t ops, double* out, hipStream_t s, const char* what) {
     hipLaunchKernelGGL(fold_kernel, dim3((unsigned)cdiv((int64_t)D * K, MT)), dim3(MT), 0, s, ws, D, P, K, ops, out);
     return check_launch(what);
 }
@@ -533,6 +701,56 @@ extern "C" int dcs_met_ssim(const float* a, const float* b, int D, int H, int W,
                        make_aff(affine, 0), make_aff(affine, 1), C1 * 2401.0, C2 * 2401.0, static_cast<double*>(ws));
     // out[z] = the sum of the map; the caller divides by (H-6)(W-6)
     return fold(static_cast<const double*>(ws), D, ntx * nty, 1, OP_ADD, out, s, "met_ssim");
+}
+
+// region records per slice: NRS per chunk of the one-pass kernel, NRSS per SSIM tile (none below 7)
+static int64_t region_parts(int H, int W) {
+    const int64_t pair = (int64_t)pair_parts(H, W) * NRS, tile = (H < 7 || W < 7) ? 0 : tiles(H - 6, W - 6) * NRSS;
+    return pair > tile ? pair : tile;
+}
+
+extern "C" size_t dcs_met_region_workspace_size(int D, int H, int W) {
+    if (!dims_ok(D, H, W)) return 0;
+    return (size_t)(region_parts(H, W) * D) * sizeof(double);
+}
+
+extern "C" int dcs_met_region_sums(const float* vue, const float* std_, const float* gen, int D, int H, int W,
+                                   const float* ranges, double* out, unsigned char* region_map, void* ws,
+                                   size_t ws_bytes, void* stream) {
+    if (!vue) return fail(DCS_E_INVALID, "met_region_sums: null pointer");
+    if (int rc = pair_args("met_region_sums", std_, gen, D, H, W, out, ws, ws_bytes, pair_parts(H, W), NRS)) return rc;
+    if (!aligned(vue, 4)) return fail(DCS_E_INVALID, "met_region_sums: misaligned pointer");
+    if (!ranges) return fail(DCS_E_INVALID, "met_region_sums: null ranges");
+    for (int i = 0; i < 6; ++i)
+        if (!(ranges[i] - ranges[i] == 0.f)) return fail(DCS_E_INVALID, "met_region_sums: the ranges must be finite");
+    const RegionRanges rr = {ranges[0], ranges[1], ranges[2], ranges[3], ranges[4], ranges[5]};
+    const int64_t S = (int64_t)H * W;
+    const int P = pair_parts(H, W);
+    const dim3 grid((unsigned)((int64_t)D * P));
+    hipStream_t s = as_stream(stream);
+    if (S % 4 == 0 && aligned(vue, 16) && aligned(std_, 16) && aligned(gen, 16) && aligned(region_map, 4))
+        hipLaunchKernelGGL(region_kernel<4>, grid, dim3(MT), 0, s, vue, std_, gen, S, P, rr, region_map,
+                           static_cast<double*>(ws));
+    else
+        hipLaunchKernelGGL(region_kernel<1>, grid, dim3(MT), 0, s, vue, std_, gen, S, P, rr, region_map,
+                           static_cast<double*>(ws));
+    return fold(static_cast<const double*>(ws), D, P, NRS, OP_ADD, out, s, "met_region_sums");
+}
+
+extern "C" int dcs_met_region_ssim(const float* std_, const float* gen, const unsigned char* region_map, int D, int H,
+                                   int W, double data_range, double* out, void* ws, size_t ws_bytes, void* stream) {
+    if (H < 7 || W < 7) return fail(DCS_E_INVALID, "met_region_ssim: the 7x7 window exceeds the image");
+    if (int rc = pair_args("met_region_ssim", std_, gen, D, H, W, out, ws, ws_bytes, tiles(H - 6, W - 6), NRSS)) return rc;
+    if (!region_map) return fail(DCS_E_INVALID, "met_region_ssim: null region map");
+    if (!(data_range - data_range == 0.0) || data_range < 0.0)
+        return fail(DCS_E_INVALID, "met_region_ssim: data_range must be finite and not negative");
+    const int ntx = (int)cdiv(W - 6, TX), nty = (int)cdiv(H - 6, TY);
+    const double C1 = (0.01 * data_range) * (0.01 * data_range), C2 = (0.03 * data_range) * (0.03 * data_range);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(region_ssim_kernel, dim3((unsigned)((int64_t)D * ntx * nty)), dim3(MT), 0, s, std_, gen, region_map,
+                       H, W, ntx, nty, C1 * 2401.0, C2 * 2401.0, static_cast<double*>(ws));
+    // out[z] = {count, sum of the map} per region; the caller divides
+    return fold(static_cast<const double*>(ws), D, ntx * nty, NRSS, OP_ADD, out, s, "met_region_ssim");
 }
 
 extern "C" int dcs_met_sobel_ts(const float* a, const float* b, int D, int H, int W, double* out, void* ws,

@@ -22,6 +22,7 @@ VOL_MAX_RADIUS, VOL_MAX_MEDIAN, VOL_MINMAX_PARTS = 16, 9, 1024
 RESIZE_MAX_TAPS = 18  # DCS_RESIZE_MAX_TAPS
 MET_NSTATS, MET_TILE_X, MET_TILE_Y, MET_PAIR_CHUNK = 9, 64, 32, 8192  # DCS_MET_*
 MET_MSSSIM_TAPS = 11
+MET_REGION_NSUMS, MET_REGION_NSSIM = 21, 8  # DCS_MET_REGION_*
 
 
 class ConvDesc(ctypes.Structure):
@@ -198,6 +199,9 @@ SIGNATURES = {
     "dcs_met_msssim_level": (c_int, [P, P, c_int, c_int, c_int, POINTER(c_double), c_double, c_double, P, P, c_size_t,
                                      P]),
     "dcs_met_pool2": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "dcs_met_region_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "dcs_met_region_sums": (c_int, [P, P, P, c_int, c_int, c_int, POINTER(c_float), P, P, P, c_size_t, P]),
+    "dcs_met_region_ssim": (c_int, [P, P, P, c_int, c_int, c_int, c_double, P, P, c_size_t, P]),
     "dcs_lpips_stem": (c_int, [P, c_int, c_int, c_int, c_float, c_float, P, P, P, P]),
     "dcs_lpips_tap_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "dcs_lpips_tap": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P]),

@@ -149,6 +149,66 @@ def pool2(a: torch.Tensor, b: torch.Tensor):
     return oa, ob
 
 
+def _region_vols(name: str, *vols):
+    """The float32 series of a region call: device, dtype, shape and contiguity are checked and
+    nothing is copied, so the kernels read what the caller holds; every fault is a ValueError."""
+    for t in vols:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name}: device tensor required (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: float32 required, got {t.dtype}")
+        if t.dim() != 3 or t.numel() == 0:
+            raise ValueError(f"{name}: non-empty [D,H,W] volume required")
+        if t.shape != vols[0].shape or t.device != vols[0].device:
+            raise ValueError(f"{name}: the volumes differ in shape or device")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous volumes required")
+    return vols
+
+
+def _region_workspace(a: torch.Tensor):
+    D, H, W = a.shape
+    n = lib.query("dcs_met_region_workspace_size", D, H, W)
+    if n == 0:
+        raise ValueError(f"metrics: unsupported volume shape {tuple(a.shape)}")
+    return torch.empty(n // 8, dtype=torch.float64, device=a.device), n
+
+
+def region_sums(vue: torch.Tensor, std: torch.Tensor, gen: torch.Tensor, ranges: Sequence[float], with_map: bool = True):
+    """(float64 [D,21], uint8 [D,H,W] or None): modules/metrics.py::region_sums of every slice from
+    one pass over the three series, and the region byte of every voxel (owner 0 lung, 1 soft,
+    2 rest, | 4 inside the true enhancement) that region_ssim_sums reads.  ranges: (lung_min,
+    lung_max, soft_min, soft_max, thr, min_hu)."""
+    vue, std, gen = _region_vols("region_sums", vue, std, gen)
+    if len(ranges) != 6:
+        raise ValueError("region_sums: ranges is (lung_min, lung_max, soft_min, soft_max, thr, min_hu)")
+    D, H, W = std.shape
+    ws, n = _region_workspace(std)
+    out = torch.empty((D, lib.MET_REGION_NSUMS), dtype=torch.float64, device=std.device)
+    rmap = torch.empty((D, H, W), dtype=torch.uint8, device=std.device) if with_map else None
+    rng = (ctypes.c_float * 6)(*[float(v) for v in ranges])
+    lib.call("dcs_met_region_sums", _p(vue), _p(std), _p(gen), D, H, W, rng, _p(out), _p(rmap), _p(ws), n, _stream())
+    return out, rmap
+
+
+def region_ssim_sums(std: torch.Tensor, gen: torch.Tensor, region_map: torch.Tensor, data_range: float) -> torch.Tensor:
+    """float64 [D,8]: per region (lung, soft, rest, true enhancement) the number of its pixels in
+    the interior cropped by 3 and the sum over them of the map ssim_sums adds up; region_map is
+    region_sums' second result for the same series."""
+    std, gen = _region_vols("region_ssim", std, gen)
+    D, H, W = std.shape
+    if H < 7 or W < 7:
+        raise ValueError("region_ssim: win_size exceeds image extent: both sides of a slice must be at least 7")
+    if (not isinstance(region_map, torch.Tensor) or region_map.device != std.device or region_map.dtype != torch.uint8
+            or region_map.shape != std.shape or not region_map.is_contiguous()):
+        raise ValueError("region_ssim: region_map must be the contiguous uint8 [D,H,W] result of region_sums")
+    ws, n = _region_workspace(std)
+    out = torch.empty((D, lib.MET_REGION_NSSIM), dtype=torch.float64, device=std.device)
+    lib.call("dcs_met_region_ssim", _p(std), _p(gen), _p(region_map), D, H, W, float(data_range), _p(out), _p(ws), n,
+             _stream())
+    return out
+
+
 def normalize(x: torch.Tensor, off: float, div: float) -> torch.Tensor:
     """(x - off) / div in float32, zeros where div is 0."""
     x = _vol(x, "normalize")

@@ -20,11 +20,14 @@ reference's own output is unpinned; the two paths here agree with each other and
 float64 formula (tests/test_cpu_msssim.py, tests/test_gpu_msssim.py).  lpips restates
 lpips.LPIPS(net='alex') with ATen on weights the user names (modules/lpips_weights.py; rules at
 ``lpips_taps``) and returns ``(nan, [])`` without them, as the reference does without the library.
+
+region_metrics (calculate.py --regions) is this package's own: the same error measures per HU-range
+owner of synthesis() and over the enhancing voxels, from three series (rules at ``REGIONS``).
 """
 from __future__ import annotations
 
 import csv
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 from scipy.ndimage import correlate1d, uniform_filter
@@ -100,8 +103,9 @@ def psnr(img1, img2) -> Result:
     return psnr_from_mse(float(np.mean(sq, dtype=np.float64)), _slice_mean(sq), max_pixel_of(a.min(), a.max()))
 
 
-def ssim_slice(s1: np.ndarray, s2: np.ndarray, data_range: float) -> float:
-    """skimage.metrics.structural_similarity with its defaults, in float64."""
+def ssim_map(s1: np.ndarray, s2: np.ndarray, data_range: float) -> np.ndarray:
+    """The full SSIM map of skimage.metrics.structural_similarity with its defaults, in float64
+    (ssim_slice averages its interior; region_ssim_sums sums it per region)."""
     if min(s1.shape) < SSIM_WIN:
         raise ValueError("win_size exceeds image extent: both sides of a slice must be at least 7")
     x, y = s1.astype(np.float64), s2.astype(np.float64)
@@ -113,7 +117,12 @@ def ssim_slice(s1: np.ndarray, s2: np.ndarray, data_range: float) -> float:
     vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
     c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
     with np.errstate(invalid="ignore", divide="ignore"):
-        s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+        return ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+
+
+def ssim_slice(s1: np.ndarray, s2: np.ndarray, data_range: float) -> float:
+    """skimage.metrics.structural_similarity with its defaults, in float64."""
+    s = ssim_map(s1, s2, data_range)
     p = (SSIM_WIN - 1) // 2
     return float(np.mean(s[p:s.shape[0] - p, p:s.shape[1] - p], dtype=np.float64))
 
@@ -461,3 +470,155 @@ def write_detail_csv(path: str, csv_data: Dict[str, list], has_vue: bool) -> Non
         w = csv.writer(f)
         w.writerow(detail_header(has_vue))
         w.writerows(detail_rows(csv_data, has_vue))
+
+
+# Region-wise evaluation (calculate.py --regions).  synthesis() hands every voxel to one owner by
+# its NCCT value: the lung model where lung_min <= vue <= lung_max, the soft-tissue model where
+# soft_min <= vue <= soft_max (lung wins where the ranges touch, as in synthesize), the NCCT
+# itself elsewhere ("rest").  Over these lies the true enhancement, (std - vue) > thr and
+# vue > min_hu with the float32 difference first and both comparisons strict, as
+# synthesize_enhancement takes them; the predicted enhancement is the same with gen for std.
+# Both paths produce the two float64 arrays below and region_from_sums derives every reported
+# number from them.  The reference has no such metric.
+REGIONS = ("lung", "soft", "rest", "enh")
+REGION_VALUES = ("n", "mae", "bias", "psnr", "ssim")
+ENH_VALUES = ("dice", "precision", "recall", "enh_true_mean", "enh_pred_mean")
+REGION_COLUMNS = tuple(f"{v}_{r}" for r in REGIONS for v in REGION_VALUES) + tuple(f"{v}_enh" for v in ENH_VALUES)
+REGION_NSUMS, REGION_NSSIM = 21, 8
+# region_sums: columns 4 r + {RS_N, RS_ABS, RS_SQ, RS_BIAS} of region r, then the five below
+RS_N, RS_ABS, RS_SQ, RS_BIAS = range(4)
+RS_TP, RS_FP, RS_FN, RS_ENH_TRUE, RS_ENH_PRED = range(16, 21)
+
+
+class RegionSpec(NamedTuple):
+    """The HU ranges of the two models and the enhancement rule, generate.py's defaults."""
+    lung_min: float = -1000.0
+    lung_max: float = -150.0
+    soft_min: float = -150.0
+    soft_max: float = 250.0
+    thr: float = 5.0
+    min_hu: float = -400.0
+
+    def ranges(self) -> Tuple[float, ...]:
+        """(lung_min, lung_max, soft_min, soft_max, thr, min_hu) as the float32 values both paths compare with."""
+        return tuple(float(np.float32(v)) for v in self)
+
+
+def _triple(vue, std, gen):
+    v, s = _pair(vue, std)
+    s, g = _pair(std, gen)
+    return v, s, g
+
+
+def region_masks(vue, std, gen, spec: RegionSpec = RegionSpec()):
+    """((lung, soft, rest, enh), pred): the membership of every voxel in float32; lung, soft and
+    rest partition the volume, pred is the predicted enhancement mask."""
+    v, s, g = _triple(vue, std, gen)
+    lmin, lmax, smin, smax, thr, mh = (np.float32(x) for x in spec)
+    lung = (v >= lmin) & (v <= lmax)
+    soft = (v >= smin) & (v <= smax) & ~lung
+    rest = ~(lung | soft)
+    valid = v > mh
+    return (lung, soft, rest, ((s - v) > thr) & valid), ((g - v) > thr) & valid
+
+
+def region_sums(vue, std, gen, spec: RegionSpec = RegionSpec()) -> np.ndarray:
+    """float64 [D,21]: per slice, for lung, soft, rest and enh in turn n, sum|std-gen|,
+    sum (std-gen)^2, sum (gen-std); then TP, FP, FN of the predicted against the true enhancement
+    mask; then sum (std-vue) and sum (gen-vue) over the true enhancement.  The differences and
+    their squares are float32, every sum is float64, counts are exact."""
+    v, s, g = _triple(vue, std, gen)
+    masks, pred = region_masks(v, s, g, spec)
+    d = s - g
+    terms = (np.abs(d), d * d, g - s)
+    et, ep = s - v, g - v
+    f64 = lambda x: float(np.sum(x, dtype=np.float64))
+    out = np.zeros((v.shape[0], REGION_NSUMS), dtype=np.float64)
+    for z in range(v.shape[0]):
+        for r, m in enumerate(masks):
+            out[z, 4 * r: 4 * r + 4] = [np.count_nonzero(m[z])] + [f64(t[z][m[z]]) for t in terms]
+        te, pe = masks[3][z], pred[z]
+        out[z, RS_TP:] = [np.count_nonzero(te & pe), np.count_nonzero(~te & pe), np.count_nonzero(te & ~pe),
+                          f64(et[z][te]), f64(ep[z][te])]
+    return out
+
+
+def region_ssim_sums(vue, std, gen, spec: RegionSpec = RegionSpec()) -> np.ndarray:
+    """float64 [D,8]: per slice and region the number of its voxels inside the crop [3:H-3, 3:W-3]
+    and the float64 sum over them of the map ssim_slice forms of (std, gen), data_range taken over
+    the whole generated volume as ssim() takes it.  Zeros where a side is below 7."""
+    v, s, g = _triple(vue, std, gen)
+    out = np.zeros((v.shape[0], REGION_NSSIM), dtype=np.float64)
+    if min(v.shape[1:]) < SSIM_WIN:
+        return out
+    masks, _ = region_masks(v, s, g, spec)
+    data_range = float(g.max() - g.min())
+    p = (SSIM_WIN - 1) // 2
+    crop = lambda x: x[p:x.shape[0] - p, p:x.shape[1] - p]
+    for z in range(v.shape[0]):
+        smap = crop(ssim_map(s[z], g[z], data_range))
+        for r, m in enumerate(masks):
+            mz = crop(m[z])
+            out[z, 2 * r: 2 * r + 2] = [np.count_nonzero(mz), float(np.sum(smap[mz], dtype=np.float64))]
+    return out
+
+
+def region_values(sums, ssim_sums, max_pixel: float) -> Dict[str, float]:
+    """The reported values of one row of region_sums and of region_ssim_sums (a slice's, or the
+    pooled sums of a volume), keyed by REGION_COLUMNS: per region n, mae, bias (mean of gen - std),
+    psnr (psnr_from_mse with the whole-volume peak) and ssim; for enh also dice, precision, recall
+    and the mean true and predicted enhancement.  nan where the denominator is 0."""
+    nan = float("nan")
+    div = lambda a, b: float(a / b) if b else nan
+    out = {}
+    for r, name in enumerate(REGIONS):
+        n, sab, ssq, sbi = (float(x) for x in sums[4 * r: 4 * r + 4])
+        out[f"n_{name}"] = int(n)
+        out[f"mae_{name}"] = div(sab, n)
+        out[f"bias_{name}"] = div(sbi, n)
+        out[f"psnr_{name}"] = psnr_from_mse(ssq / n, (), max_pixel)[0] if n else nan
+        out[f"ssim_{name}"] = div(float(ssim_sums[2 * r + 1]), float(ssim_sums[2 * r]))
+    tp, fp, fn, st, sp = (float(x) for x in sums[RS_TP:])
+    n_enh = float(sums[4 * REGIONS.index("enh") + RS_N])
+    out["dice_enh"] = div(2 * tp, 2 * tp + fp + fn)
+    out["precision_enh"] = div(tp, tp + fp)
+    out["recall_enh"] = div(tp, tp + fn)
+    out["enh_true_mean_enh"] = div(st, n_enh)
+    out["enh_pred_mean_enh"] = div(sp, n_enh)
+    return out
+
+
+def region_from_sums(sums, ssim_sums, max_pixel: float):
+    """(aggregate, per_slice) of both paths' raw arrays: per_slice maps every REGION_COLUMNS name
+    to the list of slice values; the aggregate pools over the volume, the slice sums added in
+    slice order in float64 before any division."""
+    sums, ssim_sums = np.asarray(sums, dtype=np.float64), np.asarray(ssim_sums, dtype=np.float64)
+    if sums.ndim != 2 or sums.shape[1] != REGION_NSUMS or ssim_sums.shape != (sums.shape[0], REGION_NSSIM):
+        raise ValueError("region_from_sums: [D,21] and [D,8] arrays are required")
+    rows = [region_values(a, b, max_pixel) for a, b in zip(sums, ssim_sums)]
+    tot, stot = np.zeros(REGION_NSUMS), np.zeros(REGION_NSSIM)
+    for a, b in zip(sums, ssim_sums):
+        tot, stot = tot + a, stot + b
+    return region_values(tot, stot, max_pixel), {k: [row[k] for row in rows] for k in REGION_COLUMNS}
+
+
+def region_metrics(std, gen, vue, spec: RegionSpec = RegionSpec()):
+    """The region-wise evaluation of one patient on the host: (aggregate, per_slice) of
+    region_from_sums; the series are cut to the shortest, as evaluate_patient cuts them."""
+    n = min(len(x) for x in (std, gen, vue))
+    v, s, g = _triple(vue[:n], std[:n], gen[:n])
+    return region_from_sums(region_sums(v, s, g, spec), region_ssim_sums(v, s, g, spec), max_pixel_of(s.min(), s.max()))
+
+
+def region_header() -> List[str]:
+    return ["Slice_Idx"] + list(REGION_COLUMNS)
+
+
+def write_region_csv(path: str, per_slice: Dict[str, list]) -> None:
+    """One row per slice; a value that is not defined (nan: an empty region) is an empty cell."""
+    cell = lambda x: "" if isinstance(x, float) and np.isnan(x) else x
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(region_header())
+        for i in range(len(per_slice[REGION_COLUMNS[0]])):
+            w.writerow([i] + [cell(per_slice[k][i]) for k in REGION_COLUMNS])

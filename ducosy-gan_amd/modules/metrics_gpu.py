@@ -19,7 +19,9 @@ docstring, so the two paths agree to the rounding of float64 sums taken in diffe
     torchmetrics is unpinned (modules/metrics.py);
   * LPIPS, computed only with weights, runs the AlexNet trunk on both volumes in chunks of slices
     (modules/hip/lpips.py): the first layer reads the normalised volumes and re-normalises on the
-    fly, and only the five per-slice tap sums come to the host.
+    fly, and only the five per-slice tap sums come to the host;
+  * the region-wise evaluation (``region_metrics``, calculate.py --regions) takes one pass over the
+    three series for the 21 sums of every slice and one SSIM pass that sums the map per region.
 
 Only per-slice float64 vectors come back to the host.  No CPU fallback: host tensors raise.
 """
@@ -242,6 +244,30 @@ def evaluate_pair(target, pred, device, advanced: bool = True, ms_ssim: bool = F
         out.update({"ms_ssim": ms, "lpips": lp, "emd": _emd(t, p, st),
                     "ts": _ts(t, p), "cs": st.cs(), "ed": _ed(t, p, st)})
     return out
+
+
+def region_arrays(vue: torch.Tensor, std: torch.Tensor, gen: torch.Tensor, spec: M.RegionSpec = M.RegionSpec()):
+    """(region_sums [D,21], region_ssim_sums [D,8], max_pixel) of modules/metrics.py on device
+    volumes, as host arrays: one pass for the extrema of std and gen, one over the three series
+    (it writes a byte per voxel: the region map), one for the SSIM map read against that map."""
+    st = PairStats(std, gen)
+    sums, rmap = K.region_sums(vue, std, gen, spec.ranges(), with_map=min(std.shape[1:]) >= M.SSIM_WIN)
+    if rmap is None:   # a side below 7: no SSIM cell
+        ssim_sums = np.zeros((std.shape[0], M.REGION_NSSIM), dtype=np.float64)
+    else:
+        ssim_sums = K.region_ssim_sums(std, gen, rmap, float(_rng32(st.bmin, st.bmax))).cpu().numpy()
+    return sums.cpu().numpy(), ssim_sums, M.max_pixel_of(st.amin, st.amax)
+
+
+def region_metrics(std, gen, vue, device: Optional[object] = "cuda", spec: M.RegionSpec = M.RegionSpec()):
+    """modules/metrics.py::region_metrics; ``device=None`` runs the host module.  Series that are
+    device tensors already (the ones evaluate_patient was given in the same call) are used as
+    they are: nothing is uploaded twice."""
+    if device is None:
+        return M.region_metrics(std, gen, vue, spec)
+    n = min(len(x) for x in (std, gen, vue))
+    v, s, g = (to_device(x, device)[:n].contiguous() for x in (vue, std, gen))
+    return M.region_from_sums(*region_arrays(v, s, g, spec))
 
 
 def evaluate_patient(std, gen, vue=None, device: Optional[object] = "cuda", ms_ssim: bool = False, lpips_weights=None):

@@ -711,7 +711,8 @@ int dcs_resize_nearest(const float* in, float* out, int NC, int H, int W, int oh
  * is float64 per slice.  Arithmetic: the float32 elementwise steps of the numpy expressions
  * (a - b, its square, (x - off) / div), float64 accumulation of every sum, SSIM and Sobel in
  * float64.  No floating-point atomics: per-workgroup float64 partials go to the caller's
- * workspace ws (dcs_met_workspace_size bytes serve every entry point) and are folded in a fixed
+ * workspace ws (dcs_met_workspace_size bytes serve every entry point but the two region ones,
+ * which have dcs_met_region_workspace_size) and are folded in a fixed
  * order, so results are bit-identical from run to run.  Every entry point checks its arguments on
  * the host before any launch and returns DCS_E_INVALID (DCS_E_WORKSPACE for a short workspace).
  * affine: optional HOST array {a_off, a_div, b_off, b_div}; the kernels then read
@@ -758,6 +759,28 @@ int dcs_met_msssim_level(const float* a, const float* b, int D, int H, int W, co
  * out[i][j] = float32((((x[2i][2j] + x[2i][2j+1]) + x[2i+1][2j]) + x[2i+1][2j+1]) * 0.25), the sum
  * in float64.  H, W >= 2; the outputs alias nothing. */
 int dcs_met_pool2(const float* a, const float* b, float* out_a, float* out_b, int D, int H, int W, void* stream);
+/* Region-wise evaluation (calculate.py --regions; modules/metrics.py::region_sums states it) of the
+ * three series vue (NCCT), std (CECT, the target) and gen (sCECT).  ranges: HOST array {lung_min,
+ * lung_max, soft_min, soft_max, thr, min_hu}, finite.  A voxel's owner is lung where lung_min <= vue
+ * <= lung_max, else soft where soft_min <= vue <= soft_max, else rest; the true enhancement is
+ * f32(std - vue) > thr && vue > min_hu, the predicted one the same with gen for std.
+ * out[z][0..20]: for lung, soft, rest and the true enhancement in turn n, sum|std-gen|,
+ * sum f32((std-gen)^2), sum f32(gen-std); then TP, FP, FN of the predicted against the true
+ * enhancement; then sum f32(std-vue) and sum f32(gen-vue) over the true enhancement.  Counts are exact.
+ * region_map: optional device [D][H][W] bytes, owner (0 lung, 1 soft, 2 rest) | 4 where the true
+ * enhancement holds, the input of dcs_met_region_ssim.  One pass, 12 bytes read per voxel. */
+#define DCS_MET_REGION_NSUMS 21
+#define DCS_MET_REGION_NSSIM 8
+/* bytes of workspace of the two region entry points; 0 for dimensions they refuse */
+size_t dcs_met_region_workspace_size(int D, int H, int W);
+int dcs_met_region_sums(const float* vue, const float* std_, const float* gen, int D, int H, int W,
+                        const float* ranges, double* out, unsigned char* region_map, void* ws, size_t ws_bytes,
+                        void* stream);
+/* out[z][0..7] = {number of region pixels inside the interior cropped by 3, SUM of dcs_met_ssim's
+ * map of (std, gen) over them} for lung, soft, rest and the true enhancement, read from region_map
+ * (dcs_met_region_sums wrote it).  H, W >= 7. */
+int dcs_met_region_ssim(const float* std_, const float* gen, const unsigned char* region_map, int D, int H, int W,
+                        double data_range, double* out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- LPIPS of calculate.py (lpips 0.1.4, net='alex'; modules/metrics.py::lpips_taps states it) ----
  * Activations are NHWC float32.  Layers 2-5 of the AlexNet trunk run on dcs_conv_rows (bias + ReLU

@@ -2,7 +2,7 @@
 """Host against device timing of calculate.py's per-patient metrics (modules/metrics_gpu.py::evaluate_patient).
 
     python scripts/bench_metrics.py [--shape 128x512x512] [--reps 5] [--host_reps 5] [--skip_host] [--ms_ssim]
-                                    [--lpips_weights PATH[,PATH]|random]
+                                    [--lpips_weights PATH[,PATH]|random] [--regions]
 
 One synthetic patient from modules/phantom.py (STD, a generated series = STD + rounded N(0, 20),
 a VUE series) goes through
@@ -31,6 +31,13 @@ by layer), the HIP path end to end and resident, the event time of every launch 
 summed per kernel and layer, and the
 patient end to end and resident without the switch.  ``random`` takes the seeded stand-in weights
 of the tests (modules/lpips_weights.py::random_state_dict).
+
+--regions adds under "regions" the region-wise evaluation of calculate.py --regions on the same
+patient (it changes no other leg): the host time, the device time end to end (upload of the three
+series included) and on resident series, each as median, min and max of the repeats, the event time
+of its two kernels next to pair_stats from the same run (region_sums reads three series and writes
+the region byte: 13 bytes per voxel, 12 without the map; region_ssim reads two series and the byte:
+9), and the two paths' raw arrays compared at the bars of tests/test_gpu_regions.py.
 """
 import argparse
 import json
@@ -171,6 +178,73 @@ def lpips_kernel_times(tn, pn, weights):
     return {k: round(v, 3) for k, v in out.items()}
 
 
+def _spread(times, scale=1.0, digits=4):
+    return {"median": round(statistics.median(times) * scale, digits), "min": round(min(times) * scale, digits),
+            "max": round(max(times) * scale, digits)}
+
+
+def region_times(std, gen, vue, ds, dg, dv, dev, reps, host_reps, skip_host):
+    """calculate.py --regions on the patient: both paths, the two kernels, and their agreement."""
+    spec = M.RegionSpec()
+
+    def end_to_end():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = G.region_metrics(std, gen, vue, device=dev, spec=spec)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    end_to_end()
+    out = {"device_end_to_end_s": _spread([end_to_end()[0] for _ in range(reps)])}
+    resident = lambda: G.region_metrics(ds, dg, dv, device=dev, spec=spec)
+    resident()
+    torch.cuda.synchronize()
+    out["device_resident_ms"] = _spread([_events(resident) for _ in range(reps)], digits=3)
+    sums, rmap = K.region_sums(dv, ds, dg, spec.ranges())
+    runs = {"pair_stats": (lambda: K.pair_stats(ds, dg), 8),
+            "region_sums": (lambda: K.region_sums(dv, ds, dg, spec.ranges()), 13),
+            "region_sums_no_map": (lambda: K.region_sums(dv, ds, dg, spec.ranges(), with_map=False), 12),
+            "ssim": (lambda: K.ssim_sums(ds, dg, 2500.0), 8),
+            "region_ssim": (lambda: K.region_ssim_sums(ds, dg, rmap, 2500.0), 9)}
+    out["kernels"] = {}
+    for fn, _ in runs.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in runs}
+    for _ in range(max(reps, 10)):                        # interleaved rounds: the kernels share the clock's drift
+        for name, (fn, _) in runs.items():
+            times[name].append(_events(fn))
+    for name, (_, bpv) in runs.items():
+        sp = _spread(times[name], digits=4)
+        nbytes = bpv * ds.numel()
+        out["kernels"][name] = {"ms": sp, "bytes_per_voxel": bpv,
+                                "algorithmic_GBps": {k: round(nbytes / v / 1e6, 1) for k, v in sp.items()}}
+    if not skip_host:
+        times = []
+        for i in range(host_reps + 1):
+            t0 = time.perf_counter()
+            M.region_metrics(std, gen, vue, spec)
+            times.append(time.perf_counter() - t0)
+            print(f"host regions run {i}{' (warm-up)' if i == 0 else ''}: {times[-1]:.2f} s", flush=True)
+        out["host_s"] = _spread(times[1:], digits=3)
+        want, want_ss = M.region_sums(vue, std, gen, spec), M.region_ssim_sums(vue, std, gen, spec)
+        got, got_ss, _ = G.region_arrays(dv, ds, dg, spec)
+        counts = [0, 4, 8, 12, 16, 17, 18]
+        nonneg = [1, 2, 5, 6, 9, 10, 13, 14, 19]
+        err = np.abs(got - want)
+        worst = {"counts_equal": bool(np.array_equal(got[:, counts], want[:, counts])
+                                      and np.array_equal(got_ss[:, 0::2], want_ss[:, 0::2])),
+                 "rel_nonneg": float((err[:, nonneg] / np.maximum(want[:, nonneg], 1e-300)).max()),
+                 "abs_signed_over_sum_abs": float((err[:, [3, 7, 11, 15]] / np.maximum(want[:, [1, 5, 9, 13]], 1e-300)).max()),
+                 "ssim_mean_abs": float((np.abs(got_ss[:, 1::2] - want_ss[:, 1::2]) / np.maximum(want_ss[:, 0::2], 1)).max())}
+        out["worst_error"] = worst
+        out["agree"] = bool(worst["counts_equal"] and worst["rel_nonneg"] <= 1e-10
+                            and worst["abs_signed_over_sum_abs"] <= 1e-10 and worst["ssim_mean_abs"] <= 1e-10)
+        out["speedup_end_to_end"] = round(out["host_s"]["median"] / out["device_end_to_end_s"]["median"], 1)
+        out["speedup_resident"] = round(out["host_s"]["median"] * 1e3 / out["device_resident_ms"]["median"], 1)
+    return out
+
+
 def _agree(got, want):
     worst = {"rel": 0.0, "ssim_abs": 0.0, "ms_ssim_abs": 0.0, "lpips_rel": 0.0}
     ok = True
@@ -202,6 +276,7 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--skip_host", action="store_true", help="device times only (no comparison)")
     ap.add_argument("--ms_ssim", action="store_true", help="with MS-SSIM in every leg, and its own times")
+    ap.add_argument("--regions", action="store_true", help="add the region-wise evaluation's own times")
     ap.add_argument("--lpips_weights", default=None, metavar="PATH[,PATH]|random",
                     help="with LPIPS in every leg, and its own times; 'random': the tests' seeded stand-in weights")
     a = ap.parse_args()
@@ -232,12 +307,15 @@ def main():
         times.append(dt)
         print(f"device run {i}: {dt:.4f} s", flush=True)
     res["device_end_to_end_s"] = round(statistics.median(times), 4)
+    res["device_end_to_end_spread_s"] = _spread(times)
 
     ds, dg, dv = (G.to_device(v, dev) for v in (std, gen, vue))
     resident = lambda weights=lw: G.evaluate_patient(ds, dg, dv, device=dev, ms_ssim=a.ms_ssim, lpips_weights=weights)
     resident()
     torch.cuda.synchronize()
-    res["device_resident_ms"] = round(statistics.median(_events(resident) for _ in range(a.reps)), 3)
+    times = [_events(resident) for _ in range(a.reps)]
+    res["device_resident_ms"] = round(statistics.median(times), 3)
+    res["device_resident_spread_ms"] = _spread(times, digits=3)
     res["kernels"] = kernel_times(ds, dg, a.reps)
     if a.ms_ssim:
         def alone():
@@ -252,6 +330,9 @@ def main():
               "device_resident_ms": round(_median_ms(lambda: G.ms_ssim(ds, dg), a.reps), 3)}
         res["kernels"].update(ms_ssim_times(ds, dg, a.reps))
         res["ms_ssim"] = ms
+    if a.regions:
+        res["regions"] = region_times(std, gen, vue, ds, dg, dv, dev, a.reps, a.host_reps, a.skip_host)
+        print("regions:", json.dumps(res["regions"]), flush=True)
     if lw is not None:
         def alone():
             torch.cuda.synchronize()
@@ -313,7 +394,7 @@ def main():
             res["lpips"].update({"host_s": round(statistics.median(times[1:]), 3), "host_value": val[0],
                                  "rel_error": abs(val[0] - res["lpips"]["device_value"]) / val[0]})
     print(json.dumps(res))
-    if not a.skip_host and not res["agree"]:
+    if not a.skip_host and not (res["agree"] and res.get("regions", {}).get("agree", True)):
         sys.exit(1)
 
 

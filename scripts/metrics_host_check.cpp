@@ -145,6 +145,46 @@ int main() {
     EXPECT(dcs_met_pool2(fa, fb, oa, oa, 2, 2, 2, nullptr) == DCS_E_INVALID);
     EXPECT(dcs_met_pool2(fa, fb, fa, ob, 2, 2, 2, nullptr) == DCS_E_INVALID);
     EXPECT(dcs_met_pool2(fa, fb, oa, fb, 2, 2, 2, nullptr) == DCS_E_INVALID);
+    // region-wise evaluation: its own workspace (21 per chunk or 8 per tile of the interior)
+    static unsigned char rmap[8];
+    const float ranges[6] = {-1000.f, -150.f, -150.f, 250.f, 5.f, -400.f};
+    float badr[6] = {-1000.f, -150.f, -150.f, 250.f, 5.f, nan};
+    EXPECT(dcs_met_region_workspace_size(0, 8, 8) == 0 && dcs_met_region_workspace_size(big, big, big) == 0);
+    EXPECT(dcs_met_region_workspace_size(1, 1, 1) == 21 * sizeof(double));
+    EXPECT(dcs_met_region_workspace_size(3, 33, 65) == 3 * 21 * sizeof(double));
+    EXPECT(dcs_met_region_workspace_size(2, 70, 300) == 2 * 10 * 8 * sizeof(double));   // the tiles outgrow 3 chunks
+    EXPECT(dcs_met_region_workspace_size(128, 512, 512) == 128 * 128 * 8 * sizeof(double));
+    EXPECT(dcs_met_region_workspace_size(big, 1, 1) == (size_t)big * 21 * sizeof(double));
+    const size_t needr = dcs_met_region_workspace_size(2, 8, 8);
+    EXPECT(needr == 2 * 21 * sizeof(double));
+    EXPECT(dcs_met_region_sums(nullptr, fa, fb, 2, 8, 8, ranges, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, nullptr, fb, 2, 8, 8, ranges, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, fa, nullptr, 2, 8, 8, ranges, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, fa, fb, 2, 8, 8, nullptr, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, fa, fb, 2, 8, 8, badr, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    badr[5] = -400.f, badr[0] = -inf;
+    EXPECT(dcs_met_region_sums(fa, fa, fb, 2, 8, 8, badr, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, fa, fb, 2, 8, 8, ranges, nullptr, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, fa, fb, 0, 8, 8, ranges, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, fa, fb, 2, big, big, ranges, out, rmap, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(reinterpret_cast<float*>(reinterpret_cast<char*>(fa) + 2), fa, fb, 2, 8, 8, ranges, out, rmap,
+                               ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_sums(fa, fa, fb, 2, 8, 8, ranges, out, rmap, ws, needr - 1, nullptr) == DCS_E_WORKSPACE);
+    EXPECT(dcs_met_region_ssim(fa, fb, rmap, 2, 6, 8, 1.0, out, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_ssim(fa, fb, rmap, 2, 8, 6, 1.0, out, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_ssim(fa, fb, nullptr, 2, 8, 8, 1.0, out, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_ssim(nullptr, fb, rmap, 2, 8, 8, 1.0, out, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_ssim(fa, fb, rmap, 2, 8, 8, (double)nan, out, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_ssim(fa, fb, rmap, 2, 8, 8, -1.0, out, ws, needr, nullptr) == DCS_E_INVALID);
+    EXPECT(dcs_met_region_ssim(fa, fb, rmap, 2, 8, 8, 1.0, out, ws, 2 * 8 * sizeof(double) - 1, nullptr) == DCS_E_WORKSPACE);
+    EXPECT(dcs_met_region_ssim(fa, fb, rmap, big, big, big, 1.0, out, ws, needr, nullptr) == DCS_E_INVALID);
+    for (int d = 1; d < 40; d += 7)
+        for (int h = 7; h < 700; h += 53)
+            for (int w = 7; w < 9000; w += 997) {
+                const size_t tile = (size_t)d * ((h - 6 + 31) / 32) * ((w - 6 + 63) / 64) * 8 * sizeof(double);
+                const size_t pair = (size_t)d * (((size_t)h * w + DCS_MET_PAIR_CHUNK - 1) / DCS_MET_PAIR_CHUNK) * 21 * sizeof(double);
+                EXPECT(dcs_met_region_workspace_size(d, h, w) == (tile > pair ? tile : pair));
+            }
     std::printf(failures ? "metrics host check: %d FAILED\n" : "metrics host check: ok\n", failures);
     return failures ? EXIT_FAILURE : EXIT_SUCCESS;
 }
