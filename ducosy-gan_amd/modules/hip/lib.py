@@ -23,6 +23,7 @@ RESIZE_MAX_TAPS = 18  # DCS_RESIZE_MAX_TAPS
 MET_NSTATS, MET_TILE_X, MET_TILE_Y, MET_PAIR_CHUNK = 9, 64, 32, 8192  # DCS_MET_*
 MET_MSSSIM_TAPS = 11
 MET_REGION_NSUMS, MET_REGION_NSSIM = 21, 8  # DCS_MET_REGION_*
+NMODEL_NSTATS = 11  # DCS_NMODEL_NSTATS
 
 
 class ConvDesc(ctypes.Structure):
@@ -222,6 +223,9 @@ SIGNATURES = {
     "dcs_unet_upsample2_pad_backward": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "dcs_unet_sumsq_workspace_size": (c_size_t, [c_int64]),
     "dcs_unet_sumsq": (c_int, [P, c_int64, c_float, P, P, c_size_t, P]),
+    "dcs_nmodel_targets_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "dcs_nmodel_targets": (c_int, [P, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, c_size_t,
+                                   P]),
 }
 
 

@@ -4,7 +4,8 @@
 
 The flags are the fields of modules/nmodel/config.py (defaults: the preset of --model_type), plus
 --resume [PATH] and --mma.  Data layout: <data_dir>/vue_files/<id>_vue.npy and
-<data_dir>/diff_map/<id>_diff.npy (modules/nmodel/dataset.py).  Checkpoints go to
+<data_dir>/diff_map/<id>_diff.npy (modules/nmodel/dataset.py); prepare_nmodel_data.py builds both from
+DICOM pairs (NCCT and CECT series of one acquisition) into --data_dir.  Checkpoints go to
 <output_dir>/checkpoints: latest.pth, best.pth, epoch_N.pth.
 """
 import argparse

@@ -900,6 +900,35 @@ int dcs_unet_upsample2_pad_backward(const float* dcat, int cstride, int N, int h
 size_t dcs_unet_sumsq_workspace_size(int64_t n);
 int dcs_unet_sumsq(const float* g, int64_t n, float clip, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- training targets of the normal-map U-Net from a voxel-aligned NCCT / CECT pair
+ *      (prepare_nmodel_data.py; modules/nmodel/prepare.py::residual_targets on the host) ----
+ * ncct, cect: device [D][H][W] stored values, 16 bits each, read as uint16 where the series' flag
+ * is set and as int16 otherwise, independently.  ncct_slope .. cect_intercept: device float32 [D],
+ * one rescale pair per slice and series.  merged: optional device float32 [D][H][W], the merged
+ * sCECT before the smoothing in stored-value units of the NCCT series
+ * (modules/inference.py::translate_volume_device); read only.  Per voxel with sn, in, sc, ic the
+ * slice's pairs, in float32, one IEEE operation per step (no fused multiply-add, the division
+ * correctly rounded):
+ *   x = f32(ncct) * sn + in          -> vue_out   (the NCCT in HU)
+ *   y = f32(cect) * sc + ic
+ *   g = merged * sn + in             (g = x when merged is NULL, which is then not read)
+ *   d = (y - g) / sn                 -> diff_out  (stored-value units of the NCCT: what apply_diffmap adds)
+ * so both outputs equal the host's bit for bit.  stats_out[z][0..10], float64: n, n(d >= threshold),
+ * n(d < 0), n(d > 4000), sum clip(d, 0, 4000), sum |d|, sum x, sum y, sum x^2, sum y^2, sum xy (x, y
+ * widened to float64 before they are multiplied).  Counts are exact.  One pass, 16 bytes per voxel
+ * (12 without merged), 16-byte float32 accesses when H * W % 4 == 0 and the pointers allow it.
+ * One workgroup per DCS_MET_PAIR_CHUNK voxels of a slice writes a record of DCS_NMODEL_NSTATS
+ * float64 partials to ws, a second launch folds a slice's records in index order: no atomics,
+ * bit-identical from run to run.  Arguments are checked on the host before any launch
+ * (DCS_E_INVALID; DCS_E_WORKSPACE for a short workspace); no output may alias an input. */
+#define DCS_NMODEL_NSTATS 11
+/* bytes of workspace; 0 for dimensions the entry point refuses */
+size_t dcs_nmodel_targets_workspace_size(int D, int H, int W);
+int dcs_nmodel_targets(const void* ncct, int ncct_unsigned, const float* ncct_slope, const float* ncct_intercept,
+                       const void* cect, int cect_unsigned, const float* cect_slope, const float* cect_intercept,
+                       const float* merged, int D, int H, int W, float threshold, float* vue_out, float* diff_out,
+                       double* stats_out, void* ws, size_t ws_bytes, void* stream);
+
 /* small utilities */
 int dcs_scale_add(float* y, const float* x, float a, int64_t n, void* stream); /* y += a*x */
 /* out = x * (*s) with s a device scalar (loss backward without a host sync) */
