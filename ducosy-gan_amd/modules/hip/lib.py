@@ -279,3 +279,15 @@ def call(name: str, *args) -> None:
 
 def query(name: str, *args) -> int:
     return int(getattr(load(), name)(*args))
+
+
+def ptr(t):
+    """A tensor's device pointer as a call argument; None stays None (a null pointer)."""
+    return c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream():
+    """The current torch stream as a call argument (torch imported here, as in call: importing this
+    module initialises nothing)."""
+    import torch
+    return c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -14,19 +14,12 @@ from typing import Optional, Sequence
 import torch
 
 from . import lib
+from .lib import ptr as _p, stream as _stream
 
 NSTATS = lib.MET_NSTATS
 TILE_X, TILE_Y = lib.MET_TILE_X, lib.MET_TILE_Y
 # columns of pair_stats
 SUM_ABS, SUM_SQ, SUM_AB, SUM_AA, SUM_BB, MIN_A, MAX_A, MIN_B, MAX_B = range(9)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _vol(t, name: str) -> torch.Tensor:

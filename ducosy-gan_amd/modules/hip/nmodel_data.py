@@ -7,22 +7,14 @@ is left to the caller.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import torch
 
 from . import lib
+from .lib import ptr as _p, stream as _stream
 
 NSTATS = lib.NMODEL_NSTATS
-
-
-def _p(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _stored(t, unsigned: bool, name: str):

@@ -6,8 +6,8 @@ Activations are NHWC fp32 contiguous tensors.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
-import math
 import os
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -28,28 +28,21 @@ _MMA_NAMES = {"f32": lib.MMA_F32, "bf16": lib.MMA_BF16, "bf16x3": lib.MMA_BF16X3
 # default f16x3: fp32-class (max error vs float64 <= the exact-f32 MFMA path's on every layer,
 # tests/test_gpu_mma.py::test_bf16x6_error_matches_exact_f32, also for bf16x6) at half of bf16x6's MFMAs
 _MMA = _MMA_NAMES[os.environ.get("DUCOSY_MMA", "f16x3")]
-# Path selectors below are module constants, not environment switches: the tests flip them (e.g.
-# ops._WIN = False) to hold a fused path to the one it replaced.
-# the Generator head's forward by tap projection on the MFMA pipe in the fp16 modes
-# (csrc/conv_head.hip); False = the exact-f32 VALU kernel
-_HEAD_PROJ = True
-_BPRE = True  # pre-split fp16 weight planes for the f16x3 / f16 rows pass
-_STEM = True  # the Generator stem on its MFMA kernel (csrc/conv_stem.hip)
-_PREPACK = True  # the step's weight packs in two batched launches
-_SUBWIN = True  # up-conv forwards on the sub-pixel window kernel
-_SUBWIN_D = True  # (diagnostic: their data gradients too)
-_S2WIN = True  # the down-convs on the same window phase kernels
-
-
-# residual convs in the slice-major K order (DCS_KORDER_SLICE); False = tap-major
-# IN statistics fused into the conv epilogue (ConvGeom.forward_in_stats); False = separate pass
-_FUSE_STATS = True
-_KSLICE = True
+# Path selectors: module constants, not environment switches.  Each is flipped by the test or script named
+# with it, to hold a route to the one it replaced; tests/test_gpu_dispatch.py pins the step's routing with
+# _WIN, _STEM, _WIN + _FUSE_FOLD and _SUBWIN off.
+# the Generator stem on its MFMA kernel (csrc/conv_stem.hip); False = the rows pass (tests/test_gpu_stem.py)
+_STEM = True
+# up-convs, down-convs and PatchGAN layers on the window phase kernels (csrc/conv_subpix.hip); False = the
+# rows pass (scripts/diag_grads.py)
+_SUBWIN = True
 # reflection fold of the stride-1 pad-1 data gradient in the conv epilogue (dcs_conv_dgrad_reflect);
-# False = padded-grid rows pass + dcs_reflect_fold
+# False = padded-grid rows pass + dcs_reflect_fold (tests/test_gpu_ops.py)
 _FUSE_FOLD = True
-# f16x3 residual convs on the window kernel (csrc/conv_win.hip); False = the rows pass
+# f16x3 residual convs on the window kernel (csrc/conv_win.hip); False = the rows pass (tests/test_gpu_win.py,
+# tests/test_gpu_ops.py)
 _WIN = True
+# (the two sets below: scripts/diag/f16_layers.py sets both, scripts/diag/bench_phase16.py the first)
 # window phase-kernel layers kept on f16x3 operands in the fp16 mode (ConvGeom._phase_tag).  Empty since
 # round 6: every up-conv and PatchGAN layer on fp16 operands holds the config-5 bars (the steps_64 fixture
 # pair at 0.60 of its bar, the 512 x 512 pair within 1.4e-4 / 3.7e-3 of f16x3; scripts/diag/f16_layers.py,
@@ -89,16 +82,12 @@ def get_mma() -> str:
     return {v: k for k, v in _MMA_NAMES.items()}[_MMA]
 
 
-def _p(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_p, _stream = lib.ptr, lib.stream
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _pro_ptrs(pro):
+    """The two pointers (scale, shift) of a prologue (scale, shift, act); nulls without one."""
+    return (_p(pro[0]), _p(pro[1])) if pro else (None, None)
 
 
 def _check_dev(*ts):
@@ -192,8 +181,8 @@ def range_rec(t: torch.Tensor, pro: Optional[Tuple[torch.Tensor, torch.Tensor, i
         return cached[3]
     parts = torch.empty(lib.RANGE_PARTS, device=t.device, dtype=torch.float32)
     N, C = t.shape[0], t.shape[-1]
-    lib.call("dcs_range_parts", _p(t), N, t.numel() // N, C, _p(pro[0]) if pro else None,
-             _p(pro[1]) if pro else None, pro[2] if pro else ACT_NONE, _p(parts), _stream())
+    lib.call("dcs_range_parts", _p(t), N, t.numel() // N, C, *_pro_ptrs(pro), pro[2] if pro else ACT_NONE, _p(parts),
+             _stream())
     t._dcs_rng = (t._version, pro[0] if pro else None, pro[2] if pro else ACT_NONE, parts)
     return parts
 
@@ -353,7 +342,7 @@ def bump_weights_epoch(params=None) -> None:
 
 
 def _cached_pack(w: torch.Tensor, key, make):
-    stamp = (w.data_ptr(), w._version, _EPOCH[0], getattr(w, "_dcs_epoch", 0), _MMA, _WIN, _KSLICE)
+    stamp = (w.data_ptr(), w._version, _EPOCH[0], getattr(w, "_dcs_epoch", 0), _MMA, _WIN)
     c = getattr(w, "_dcs_packs", None)
     if c is None or c[0] != stamp:
         c = (stamp, {})
@@ -415,7 +404,7 @@ def prepack(params) -> None:
     one or two small launches per pack at first use.  The packs land in the same cache, so the
     step's own calls find them; their values equal the per-pack calls'."""
     global _BATCH
-    if _BATCH is not None or not _PREPACK:
+    if _BATCH is not None:
         return
     b = _PackBatch()
     dev = None
@@ -461,7 +450,7 @@ class ConvGeom:
         DCS_KORDER_SLICE: 3.7x fewer L2 misses on the gathered rows, 4 % faster in bf16x6) in the
         bf16 operand modes; their packed weights follow it.  The exact-f32 kernel keeps the
         tap-major order (its gather decodes the tap once per 8 k-tiles there)."""
-        return _is_res_geom(self) and _KSLICE and _MMA != lib.MMA_F32
+        return _is_res_geom(self) and _MMA != lib.MMA_F32
 
     def out_hw(self, H, W):
         Hv, Wv = H * self.up, W * self.up
@@ -503,6 +492,8 @@ class ConvGeom:
             scratch = workspace(lib.query("dcs_pack_weights_h3_scratch_size"), w.device)
             lib.call("dcs_pack_weights_h3", _p(w), self.cout, self.cin, flip, ncols, _p(hi), _p(lo), _p(scratch),
                      _p(wexp), _stream())
+        # a pack carries the planes of one window route at most (ConvGeom._forward walks them in one order)
+        assert not hasattr(wpack, "_dcs_sp")
         wpack._dcs_h3 = (hi, lo, wexp)
         return wpack
 
@@ -516,7 +507,7 @@ class ConvGeom:
     def s2win(self) -> bool:
         """The window phase kernels for this stride-2 3x3 or 4x4 zero-pad-1 conv (the down-convs, the
         PatchGAN layers): forward over the source's parity classes, data gradient over dx's."""
-        return (_SUBWIN and _S2WIN and _h3() and self.stride == 2 and self.k in (3, 4) and self.up == 1 and
+        return (_SUBWIN and _h3() and self.stride == 2 and self.k in (3, 4) and self.up == 1 and
                 self.pads == (1, 1, 1, 1) and self.pad_mode == DCS_PAD_ZERO and self.cout % 128 == 0 and
                 self.cin % 64 == 0)
 
@@ -535,6 +526,7 @@ class ConvGeom:
         else:
             lib.call("dcs_pack_subpix_h3", _p(w), self.cout, self.cin, kind, _p(hi), _p(lo), _p(scratch), _p(wexp),
                      _stream())
+        assert not hasattr(wpack, "_dcs_h3")  # as in _attach_h3
         wpack._dcs_sp = (hi, lo, wexp)
         return wpack
 
@@ -592,7 +584,7 @@ class ConvGeom:
             return self._pack(w, 2, 1, self.k * self.k * self.cout, 1)
         if self.subpixel and ci > 4:
             out = self._pack(w, 4, ci, 16 * self.cout, ci)
-            return self._attach_sp(out, w, 1) if (self.subwin and _SUBWIN_D and ci == self.cin and ci % 128 == 0) else out
+            return self._attach_sp(out, w, 1) if (self.subwin and ci == self.cin and ci % 128 == 0) else out
         kind = 2 if self.stride == 2 else 1
         K = self.k * self.k * self.cout
         out = self._pack(w, kind, ci, K, ci)
@@ -615,7 +607,7 @@ class ConvGeom:
             rng = torch.empty(lib.RANGE_PARTS, device=w.device, dtype=torch.float32)
             out._dcs_rng = (out._version, None, ACT_NONE, rng)
             planes = None
-            if _BPRE and not self.win:  # pre-split fp16 planes for the rows pass (dcs_conv_desc.b_h3)
+            if not self.win:  # pre-split fp16 planes for the rows pass (dcs_conv_desc.b_h3)
                 planes = torch.empty(cols * 2 * Kpad, device=w.device, dtype=torch.float16)
                 out._dcs_bh3 = (out._version, planes)
             if _BATCH is not None:
@@ -632,10 +624,6 @@ class ConvGeom:
             lib.call("dcs_pack_weights", _p(w), self.cout, self.cin, self.k, self.k, kind, ci_count, Kpad,
                      cols, nmajor, _p(out), _stream())
         return out
-
-    @staticmethod
-    def _ldb(wpack: torch.Tensor, narrow: bool) -> int:
-        return wpack.shape[1]  # Kpad (N-major) or columns (K-major): always the inner dim
 
     # ---- descriptors ---------------------------------------------------------------
     def _desc_fwd(self, s: Src, ldb: int, pro_act: int, epi_act: int, rows: bool = True) -> lib.ConvDesc:
@@ -658,49 +646,79 @@ class ConvGeom:
         return d
 
     # ---- forward -------------------------------------------------------------------
+    def forward(self, s: Src, wpack: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                pro: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
+                epi_act: int = ACT_NONE, pro_max: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``pro_max``: per-(image, channel) max of the source before its prologue (INStats.xmax), for
+        the Generator head's tap-projection kernel in the fp16 modes (csrc/conv_head.hip)."""
+        return self._forward(s, wpack, bias, pro, epi_act, pro_max, False, False)
+
     def forward_in_stats(self, s: Src, wpack: torch.Tensor, bias: Optional[torch.Tensor] = None,
                          pro: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
                          epi_act: int = ACT_NONE, want_max: bool = False):
         """forward() and the InstanceNorm statistics of its output (the IN that follows every
-        Generator / PatchGAN conv, modules/model.py:94-111, 124-129).  Where the rows pass applies
-        (Ho*Wo % 128 == 0) the per-tile partials come out of the conv epilogue
-        (dcs_conv_rows_in_stats) and one small kernel merges them (dcs_in_stats_finish): the
-        statistics pass's re-read of the output is gone.  Otherwise: forward + in_stats."""
-        Ho, Wo = self.out_hw(s.H, s.W)
-        d = self._desc_fwd(s, wpack.shape[1], pro[2] if pro is not None else ACT_NONE, epi_act)
-        nb = 0 if (self.narrow or not _FUSE_STATS) else lib.query("dcs_conv_rows_in_stats_parts_size", ctypes.byref(d))
-        if nb and s.t2 is None:
-            _set_mma(d, s.t, pro, _wrng(wpack), wpack)
-        if nb and _STEM and bias is None and lib.query("dcs_stem_fwd_ok", ctypes.byref(d)):
-            return self._stem(s, d, wpack, True, want_max)
-        h3 = getattr(wpack, "_dcs_h3", None)
-        if nb and h3 is not None and bias is None and lib.query("dcs_conv3_win_ok", ctypes.byref(d), 0):
-            return self._win_in_stats(s, d, h3, nb, want_max)
-        sp = getattr(wpack, "_dcs_sp", None)
-        if nb and sp is not None and bias is None and s.t2 is None and self._phase_win_ok(d):
-            return self._subpix(s, d, sp, True, want_max, pro)
-        if nb == 0:
-            out = self.forward(s, wpack, bias, pro, epi_act)
-            return out, in_stats(out, want_max)
+        Generator / PatchGAN conv, modules/model.py:94-111, 124-129).  Where the rows pass's tiles
+        apply (Ho*Wo % 128 == 0) the per-tile partials come out of the conv epilogue of whichever kernel
+        runs the layer and one small kernel merges them (dcs_in_stats_finish): the statistics pass's
+        re-read of the output is gone.  Otherwise: forward + in_stats."""
+        return self._forward(s, wpack, bias, pro, epi_act, None, True, want_max)
+
+    @contextlib.contextmanager
+    def _probe(self, npix: int, ci: int):
+        """PROBE's events around a launch of the residual geometry, with its algorithmic FLOPs."""
+        e0 = PROBE.begin() if _is_res_geom(self) else None
+        yield
+        PROBE.end(e0, 2.0 * npix * self.cout * ci * self.k * self.k)
+
+    def _forward(self, s: Src, wpack, bias, pro, epi_act, pro_max, stats: bool, want_max: bool):
+        """The forward router: the first route that applies, in the order head projection, stem, window,
+        window phase kernels, rows pass (narrow kernel for cout <= 4).  A new route is one more candidate
+        here.  At most one of the four special routes can apply to a layer -- the head is narrow, the
+        others are not; the stem's pack (cin_pad) carries no planes; a pack carries one of _dcs_h3 /
+        _dcs_sp at most (asserted in _attach_h3 / _attach_sp) -- so their order decides nothing.
+        ``stats``: also the IN statistics of the output, returned as (out, INStats)."""
         assert s.C == self.cin or (s.C == 4 and self.cin < 4), (s.C, self.cin)
         _check_dev(s.t, s.t2, wpack, bias)
+        d = self._desc_fwd(s, wpack.shape[1], pro[2] if pro is not None else ACT_NONE, epi_act)
+        nb = 0
+        if stats:
+            nb = 0 if self.narrow else lib.query("dcs_conv_rows_in_stats_parts_size", ctypes.byref(d))
+            if nb == 0:  # no per-tile partials for this shape: the plain forward, then a statistics pass
+                out = self._forward(s, wpack, bias, pro, epi_act, None, False, False)
+                return out, in_stats(out, want_max)
+        Ho, Wo = d.Ho, d.Wo
         dev = s.t.device
+        if self.narrow and pro is not None and pro_max is not None and _h3() and s.t2 is None:
+            d.mma = _fixed_mma("head")
+            if lib.query("dcs_head_fwd_proj_ok", ctypes.byref(d)):
+                out = torch.empty(s.N, Ho, Wo, self.cout, device=dev, dtype=torch.float32)
+                lib.call("dcs_head_fwd_proj", ctypes.byref(d), _p(s.t), _p(wpack), _p(bias), *_pro_ptrs(pro),
+                         _p(pro_max), _p(out), _stream())
+                return out
+            d.mma = _fallback()
+        ranged = not self.narrow and s.t2 is None  # one contiguous source: the fp16 modes' range records
+        if ranged:
+            _set_mma(d, s.t, pro, _wrng(wpack), wpack)
+        if ranged and _STEM and bias is None and lib.query("dcs_stem_fwd_ok", ctypes.byref(d)):
+            return self._stem(s, d, wpack, stats, want_max)
+        h3 = getattr(wpack, "_dcs_h3", None)
+        if h3 is not None and bias is None and lib.query("dcs_conv3_win_ok", ctypes.byref(d), 0):
+            return self._win(s, d, h3, nb, stats, want_max)
+        sp = getattr(wpack, "_dcs_sp", None)
+        if ranged and sp is not None and bias is None and self._phase_win_ok(d):
+            return self._subpix(s, d, sp, stats, want_max, pro)
         out = torch.empty(s.N, Ho, Wo, self.cout, device=dev, dtype=torch.float32)
+        if not stats:
+            with self._probe(s.N * Ho * Wo, self.cin):
+                lib.call("dcs_conv_rows_narrow" if self.narrow else "dcs_conv_rows", ctypes.byref(d), _p(s.t),
+                         _p(s.t2), _p(wpack), _p(bias), *_pro_ptrs(pro), _p(out), _stream())
+            return out
         parts = workspace(nb, dev)
         nchunk = ctypes.c_int(0)
-        e0 = PROBE.begin() if _is_res_geom(self) else None
-        lib.call("dcs_conv_rows_in_stats", ctypes.byref(d), _p(s.t), _p(s.t2), _p(wpack), _p(bias),
-                 _p(pro[0]) if pro else None, _p(pro[1]) if pro else None, _p(out), _p(parts), parts.numel(),
-                 ctypes.byref(nchunk), _stream())
-        PROBE.end(e0, 2.0 * s.N * Ho * Wo * self.cout * self.cin * self.k * self.k)
-        C = self.cout
-        scale = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        shift = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        xmax = torch.empty(s.N, C, device=dev, dtype=torch.float32) if want_max else None
-        xam = torch.empty(s.N, C, device=dev, dtype=torch.int32) if want_max else None
-        lib.call("dcs_in_stats_finish", _p(parts), s.N, C, nchunk.value, IN_EPS, _p(scale), _p(shift), _p(xmax),
-                 _p(xam), _stream())
-        return out, INStats(scale, shift, xmax, xam)
+        with self._probe(s.N * Ho * Wo, self.cin):
+            lib.call("dcs_conv_rows_in_stats", ctypes.byref(d), _p(s.t), _p(s.t2), _p(wpack), _p(bias),
+                     *_pro_ptrs(pro), _p(out), _p(parts), parts.numel(), ctypes.byref(nchunk), _stream())
+        return out, _in_finish(parts, nchunk.value, s.N, self.cout, dev, want_max)
 
     def _stem(self, s: Src, d, wpack, stats: bool, want_max: bool = False):
         """The Generator stem (7x7 reflect-pad-3, NHWC x 4 source -> 64) on its MFMA kernel
@@ -712,16 +730,7 @@ class ConvGeom:
         nchunk = ctypes.c_int(0)
         lib.call("dcs_stem_fwd", ctypes.byref(d), _p(s.t), _p(wpack), _p(out), _p(parts),
                  parts.numel() if stats else 0, ctypes.byref(nchunk), _stream())
-        if not stats:
-            return out
-        C = self.cout
-        scale = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        shift = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        xmax = torch.empty(s.N, C, device=dev, dtype=torch.float32) if want_max else None
-        xam = torch.empty(s.N, C, device=dev, dtype=torch.int32) if want_max else None
-        lib.call("dcs_in_stats_finish", _p(parts), s.N, C, nchunk.value, IN_EPS, _p(scale), _p(shift), _p(xmax),
-                 _p(xam), _stream())
-        return out, INStats(scale, shift, xmax, xam)
+        return (out, _in_finish(parts, nchunk.value, s.N, self.cout, dev, want_max)) if stats else out
 
     def _phase_tag(self) -> Optional[str]:
         """The layer's key in _PHASE_F16X3: "up1" / "up2" (the up-convs 256->128, 128->64), "pg64" /
@@ -751,24 +760,14 @@ class ConvGeom:
         ``stats``) on the window phase kernels (csrc/conv_subpix.hip), operand mode as _phase_mma."""
         dev = s.t.device
         self._phase_mma(d)
-        Ho, Wo = self.out_hw(s.H, s.W)
-        out = torch.empty(s.N, Ho, Wo, self.cout, device=dev, dtype=torch.float32)
+        out = torch.empty(s.N, d.Ho, d.Wo, self.cout, device=dev, dtype=torch.float32)
         api = "dcs_subpix_win" if self.subpixel else "dcs_stride2_win"
         parts = workspace(lib.query(api + "_parts_size", ctypes.byref(d)), dev) if stats else None
         nchunk = ctypes.c_int(0)
-        pre = () if self.subpixel else (_p(pro[0]) if pro else None, _p(pro[1]) if pro else None)
+        pre = () if self.subpixel else _pro_ptrs(pro)
         lib.call(api, ctypes.byref(d), _p(s.t), *pre, _p(sp[0]), _p(sp[1]), _p(sp[2]), _p(out), _p(parts),
                  parts.numel() if stats else 0, ctypes.byref(nchunk), _stream())
-        if not stats:
-            return out
-        C = self.cout
-        scale = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        shift = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        xmax = torch.empty(s.N, C, device=dev, dtype=torch.float32) if want_max else None
-        xam = torch.empty(s.N, C, device=dev, dtype=torch.int32) if want_max else None
-        lib.call("dcs_in_stats_finish", _p(parts), s.N, C, nchunk.value, IN_EPS, _p(scale), _p(shift), _p(xmax),
-                 _p(xam), _stream())
-        return out, INStats(scale, shift, xmax, xam)
+        return (out, _in_finish(parts, nchunk.value, s.N, self.cout, dev, want_max)) if stats else out
 
     def _phase_win(self, d, dy: torch.Tensor, sp, out: torch.Tensor) -> bool:
         """An up- or down-conv (or PatchGAN layer) data gradient on the window phase kernels
@@ -787,64 +786,66 @@ class ConvGeom:
         d.mma = mma
         return False
 
-    def _win_in_stats(self, s: Src, d, h3, nb, want_max):
-        """Forward + IN statistics on the f16x3 window kernel (csrc/conv_win.hip)."""
+    def _win(self, s: Src, d, h3, nb, stats: bool, want_max: bool = False):
+        """Forward on the f16x3 window kernel (csrc/conv_win.hip), with the IN statistics of its output
+        when ``stats`` (``nb``: bytes of their per-tile partials)."""
         dev = s.t.device
-        Ho, Wo = self.out_hw(s.H, s.W)
-        out = torch.empty(s.N, Ho, Wo, self.cout, device=dev, dtype=torch.float32)
-        parts = workspace(nb, dev)
+        out = torch.empty(s.N, d.Ho, d.Wo, self.cout, device=dev, dtype=torch.float32)
+        parts = workspace(nb, dev) if stats else None
         nchunk = ctypes.c_int(0)
-        e0 = PROBE.begin() if _is_res_geom(self) else None
-        lib.call("dcs_conv3_win_in_stats", ctypes.byref(d), _p(s.t), _p(h3[0]), _p(h3[1]), _p(h3[2]), _p(out),
-                 _p(parts), parts.numel(), ctypes.byref(nchunk), _stream())
-        PROBE.end(e0, 2.0 * s.N * Ho * Wo * self.cout * self.cin * self.k * self.k)
-        C = self.cout
-        scale = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        shift = torch.empty(s.N, C, device=dev, dtype=torch.float32)
-        xmax = torch.empty(s.N, C, device=dev, dtype=torch.float32) if want_max else None
-        xam = torch.empty(s.N, C, device=dev, dtype=torch.int32) if want_max else None
-        lib.call("dcs_in_stats_finish", _p(parts), s.N, C, nchunk.value, IN_EPS, _p(scale), _p(shift), _p(xmax),
-                 _p(xam), _stream())
-        return out, INStats(scale, shift, xmax, xam)
-
-    def forward(self, s: Src, wpack: torch.Tensor, bias: Optional[torch.Tensor] = None,
-                pro: Optional[Tuple[torch.Tensor, torch.Tensor, int]] = None,
-                epi_act: int = ACT_NONE, pro_max: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``pro_max``: per-(image, channel) max of the source before its prologue (INStats.xmax), for
-        the Generator head's tap-projection kernel in the fp16 modes (csrc/conv_head.hip)."""
-        assert s.C == self.cin or (s.C == 4 and self.cin < 4), (s.C, self.cin)
-        _check_dev(s.t, s.t2, wpack, bias)
-        Ho, Wo = self.out_hw(s.H, s.W)
-        pro_act = pro[2] if pro is not None else ACT_NONE
-        d = self._desc_fwd(s, wpack.shape[1], pro_act, epi_act)
-        out = torch.empty(s.N, Ho, Wo, self.cout, device=s.t.device, dtype=torch.float32)
-        if self.narrow and _HEAD_PROJ and pro is not None and pro_max is not None and _h3() and s.t2 is None:
-            d.mma = _fixed_mma("head")
-            if lib.query("dcs_head_fwd_proj_ok", ctypes.byref(d)):
-                lib.call("dcs_head_fwd_proj", ctypes.byref(d), _p(s.t), _p(wpack), _p(bias), _p(pro[0]), _p(pro[1]),
-                         _p(pro_max), _p(out), _stream())
-                return out
-            d.mma = _fallback()
-        fn = "dcs_conv_rows_narrow" if self.narrow else "dcs_conv_rows"
-        if not self.narrow and s.t2 is None:
-            _set_mma(d, s.t, pro, _wrng(wpack), wpack)
-            if _STEM and bias is None and lib.query("dcs_stem_fwd_ok", ctypes.byref(d)):
-                return self._stem(s, d, wpack, False)
-            sp = getattr(wpack, "_dcs_sp", None)
-            if sp is not None and bias is None and self._phase_win_ok(d):
-                return self._subpix(s, d, sp, False, pro=pro)
-        h3 = getattr(wpack, "_dcs_h3", None)
-        e0 = PROBE.begin() if _is_res_geom(self) else None
-        if h3 is not None and bias is None and lib.query("dcs_conv3_win_ok", ctypes.byref(d), 0):
+        with self._probe(s.N * d.Ho * d.Wo, self.cin):
             lib.call("dcs_conv3_win_in_stats", ctypes.byref(d), _p(s.t), _p(h3[0]), _p(h3[1]), _p(h3[2]), _p(out),
-                     None, 0, None, _stream())
-        else:
-            lib.call(fn, ctypes.byref(d), _p(s.t), _p(s.t2), _p(wpack), _p(bias),
-                     _p(pro[0]) if pro else None, _p(pro[1]) if pro else None, _p(out), _stream())
-        PROBE.end(e0, 2.0 * s.N * Ho * Wo * self.cout * self.cin * self.k * self.k)
-        return out
+                     _p(parts), parts.numel() if stats else 0, ctypes.byref(nchunk) if stats else None, _stream())
+        return (out, _in_finish(parts, nchunk.value, s.N, self.cout, dev, want_max)) if stats else out
 
     # ---- data gradient ---------------------------------------------------------------
+    def _desc_dgrad(self, dy: torch.Tensor, wpack_d: torch.Tensor, ci: int, H: int, W: int) -> lib.ConvDesc:
+        """The data gradient onto ``ci`` input channels of an H x W input as a zero-padded convolution over
+        dy with the pack's flipped taps, in one of four geometries: the sub-pixel forward's adjoint (4x4
+        stride 2 over dy, parity 0), a stride-2 conv's (parity 1), a reflect-padded conv's on the padded
+        grid (pt = pl = k - 1; the caller folds the ring back), and the plain one on the upsampled grid."""
+        N, Ho, Wo, Co = dy.shape
+        d = lib.ConvDesc()
+        d.N, d.Hs, d.Ws, d.Cs = N, Ho, Wo, Co
+        d.s_n, d.s_c, d.s_h, d.s_w = Ho * Wo * Co, 1, Wo * Co, Co
+        d.csplit = Co
+        d.up, d.pad_mode = 1, DCS_PAD_ZERO
+        d.KH = d.KW = self.k
+        d.ldb, d.pro_act, d.epi_act = wpack_d.shape[1], ACT_NONE, ACT_NONE
+        d.mma = _fallback() if _h3() else _MMA
+        if ci > 4:
+            # always with the pack: a window pack (_dcs_h3) carries no _dcs_bh3 for _set_mma to find (_pack
+            # attaches those planes only when not self.win), so its descriptors keep b_h3 null either way
+            _set_mma(d, dy, None, _wrng(wpack_d), wpack_d)
+        # kslice holds for the residual geometry alone, which is neither sub-pixel nor stride 2: the window
+        # phase kernels' descriptors are tap-major by this line too
+        d.korder = lib.KORDER_SLICE if (self.kslice and ci > 4) else lib.KORDER_TAP
+        d.Co = ci
+        t, l, b, r = self.pads
+        if self.subpixel and ci > 4:  # a 4x4 stride-2 pad-1 conv over dy (kind-4 pack)
+            d.KH = d.KW = 4
+            d.stride, d.parity, d.pt, d.pl = 2, 0, 1, 1
+            d.Ho, d.Wo = H, W
+        elif self.stride == 2:
+            assert self.up == 1 and self.pad_mode == DCS_PAD_ZERO
+            d.stride, d.parity, d.pt, d.pl = 2, 1, t, l
+            d.Ho, d.Wo = H, W
+        elif self.pad_mode == DCS_PAD_REFLECT:
+            assert self.up == 1 and t == b and l == r and t == l
+            d.stride, d.parity = 1, 0
+            d.pt = d.pl = self.k - 1
+            d.Ho, d.Wo = H + 2 * t, W + 2 * t
+        else:
+            d.stride, d.parity = 1, 0
+            d.pt, d.pl = self.k - 1 - t, self.k - 1 - l
+            d.Ho, d.Wo = H * self.up, W * self.up
+        return d
+
+    @staticmethod
+    def _rows_dgrad(d, dy, wpack_d, out) -> None:
+        lib.call("dcs_conv_rows_narrow" if d.Co <= 4 else "dcs_conv_rows", ctypes.byref(d), _p(dy), None, _p(wpack_d),
+                 None, None, None, _p(out), _stream())
+
     def dgrad(self, dy: torch.Tensor, wpack_d: torch.Tensor, H: int, W: int,
               ci_count: Optional[int] = None, addend: Optional[torch.Tensor] = None, inbwd=None):
         """dL/d(input) [N,H,W,ci] (NHWC) of this conv given dy [N,Ho,Wo,cout] (NHWC).  ``inbwd`` = (y,
@@ -862,113 +863,70 @@ class ConvGeom:
         N, Ho, Wo, Co = dy.shape
         assert Co == self.cout
         ci = self.cin if ci_count is None else ci_count
+        dev = dy.device
         if self.c1_dgrad and ci == self.cin:
-            out = torch.empty(N, H, W, ci, device=dy.device, dtype=torch.float32)
+            out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
             lib.call("dcs_conv_dgrad_c1", _p(dy.contiguous()), N, H, W, _p(wpack_d), ci, self.k, self.pads[0],
                      self.pad_mode, _p(out), _stream())
-            if addend is not None:
-                lib.call("dcs_scale_add", _p(out), _p(addend), 1.0, out.numel(), _stream())
-            return out
-        if self.to1_dgrad(ci):
-            out = torch.empty(N, H, W, 1, device=dy.device, dtype=torch.float32)
+        elif self.to1_dgrad(ci):
+            out = torch.empty(N, H, W, 1, device=dev, dtype=torch.float32)
             dyc = dy.contiguous()
             ws = torch.empty(lib.query("dcs_conv_dgrad_to1_workspace_size", N, Ho, Wo, self.k) // 4,
-                             device=dy.device, dtype=torch.float32)
+                             device=dev, dtype=torch.float32)
             lib.call("dcs_conv_dgrad_to1", _p(dyc), N, Ho, Wo, Co, _p(wpack_d), self.k, self.stride,
                      self.pads[0], self.pads[1], self.pad_mode, H, W, _p(out), _p(ws), ws.numel() * 4, _stream())
-            if addend is not None:
-                lib.call("dcs_scale_add", _p(out), _p(addend), 1.0, out.numel(), _stream())
-            return out
-        narrow = ci <= 4
-        fn = "dcs_conv_rows_narrow" if narrow else "dcs_conv_rows"
-        d = lib.ConvDesc()
-        d.N, d.Hs, d.Ws, d.Cs = N, Ho, Wo, Co
-        d.s_n, d.s_c, d.s_h, d.s_w = Ho * Wo * Co, 1, Wo * Co, Co
-        d.csplit = Co
-        d.up, d.pad_mode = 1, DCS_PAD_ZERO
-        d.KH = d.KW = self.k
-        d.ldb, d.pro_act, d.epi_act = wpack_d.shape[1], ACT_NONE, ACT_NONE
-        d.mma = _fallback() if _h3() else _MMA
-        if not narrow:
-            _set_mma(d, dy, None, _wrng(wpack_d), wpack_d)
-        d.korder = lib.KORDER_SLICE if (self.kslice and ci > 4) else lib.KORDER_TAP
-        d.Co = ci
-        dev = dy.device
-        t, l, b, r = self.pads
-        if self.subpixel and not narrow:
-            # adjoint of the sub-pixel forward: a 4x4 stride-2 pad-1 conv over dy (kind-4 pack)
-            d.KH = d.KW = 4
-            d.stride, d.parity, d.pt, d.pl = 2, 0, 1, 1
-            d.Ho, d.Wo = H, W
-            out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
-            sp = getattr(wpack_d, "_dcs_sp", None)
-            if sp is None or narrow or not self._phase_win(d, dy, sp, out):
-                lib.call(fn, ctypes.byref(d), _p(dy), None, _p(wpack_d), None, None, None, _p(out), _stream())
-            if addend is not None:
-                lib.call("dcs_scale_add", _p(out), _p(addend), 1.0, out.numel(), _stream())
-            return out
-        if self.stride == 2:
-            assert self.up == 1 and self.pad_mode == DCS_PAD_ZERO
-            d.stride, d.parity, d.pt, d.pl = 2, 1, t, l
-            d.Ho, d.Wo = H, W
-            out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
-            sp = getattr(wpack_d, "_dcs_sp", None)
-            if sp is None or narrow or not self._phase_win(d, dy, sp, out):
-                lib.call(fn, ctypes.byref(d), _p(dy), None, _p(wpack_d), None, None, None, _p(out),
-                         _stream())
-            if addend is not None:
-                lib.call("dcs_scale_add", _p(out), _p(addend), 1.0, out.numel(), _stream())
-            return out
-        d.stride, d.parity = 1, 0
-        Hv, Wv = H * self.up, W * self.up
-        if self.pad_mode == DCS_PAD_REFLECT:
-            assert self.up == 1 and t == b and l == r and t == l
-            p = t
-            d.pt = d.pl = self.k - 1
-            d.Ho, d.Wo = Hv + 2 * p, Wv + 2 * p
-            h3 = getattr(wpack_d, "_dcs_h3", None)
-            if h3 is not None and not narrow and dy.is_contiguous() and \
-                    lib.query("dcs_conv3_win_ok", ctypes.byref(d), 1):
-                out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
-                ring = torch.empty(lib.query("dcs_conv_dgrad_reflect_ring_size", ctypes.byref(d)) // 4,
-                                   device=dev, dtype=torch.float32)
-                e0 = PROBE.begin() if _is_res_geom(self) else None
-                lib.call("dcs_conv_dgrad_reflect_win", ctypes.byref(d), _p(dy), _p(wpack_d), _p(h3[0]), _p(h3[1]),
-                         _p(h3[2]), _p(addend), _p(out), _p(ring), _stream())
-                PROBE.end(e0, 2.0 * N * H * W * self.cout * ci * self.k * self.k)
-                return out
-            if _FUSE_FOLD and addend is None and p == 1 and self.k == 3 and H >= 4 and W >= 4 and not narrow \
-                    and dy.is_contiguous() and ci % 4 == 0:
-                # interior written by the conv epilogue, the ring folded in after.  With a residual
-                # addend the padded pass + dcs_reflect_fold stays faster: the addend read in the
-                # epilogue sits after the MFMA loop (+145 us per 16-image launch against +125 us for
-                # the whole fold pass, profiles/r02e_kernel_table.md)
-                ring = lib.query("dcs_conv_dgrad_reflect_ring_size", ctypes.byref(d)) // 4
-                buf = torch.empty(N * H * W * ci + ring, device=dev, dtype=torch.float32)
-                out = buf[:N * H * W * ci].view(N, H, W, ci)
-                e0 = PROBE.begin() if _is_res_geom(self) else None
-                lib.call("dcs_conv_dgrad_reflect", ctypes.byref(d), _p(dy), _p(wpack_d), None, _p(out),
-                         ctypes.c_void_p(buf.data_ptr() + N * H * W * ci * 4), _stream())
-                PROBE.end(e0, 2.0 * N * Ho * Wo * self.cout * ci * self.k * self.k)
-                return out
-            dpad = torch.empty(N, d.Ho, d.Wo, ci, device=dev, dtype=torch.float32)
-            e0 = PROBE.begin() if _is_res_geom(self) else None
-            lib.call(fn, ctypes.byref(d), _p(dy), None, _p(wpack_d), None, None, None, _p(dpad), _stream())
-            PROBE.end(e0, 2.0 * N * Ho * Wo * self.cout * ci * self.k * self.k)
-            out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
-            lib.call("dcs_reflect_fold", _p(dpad), _p(addend), _p(out), N, H, W, ci, p, _stream())
-            return out
-        d.pt, d.pl = self.k - 1 - t, self.k - 1 - l
-        d.Ho, d.Wo = Hv, Wv
-        dv = torch.empty(N, Hv, Wv, ci, device=dev, dtype=torch.float32)
-        lib.call(fn, ctypes.byref(d), _p(dy), None, _p(wpack_d), None, None, None, _p(dv), _stream())
-        if self.up == 2:
-            out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
-            lib.call("dcs_upsample2_grad", _p(dv), _p(out), N, H, W, ci, _stream())
         else:
-            out = dv
+            d = self._desc_dgrad(dy, wpack_d, ci, H, W)
+            if d.stride == 1 and self.pad_mode == DCS_PAD_REFLECT:
+                return self._dgrad_reflect(d, dy, wpack_d, H, W, ci, addend)  # the addend goes in its kernels
+            if d.stride == 2:  # the sub-pixel adjoint or a stride-2 conv: the window phase kernels' geometries
+                out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
+                sp = getattr(wpack_d, "_dcs_sp", None)
+                if sp is None or ci <= 4 or not self._phase_win(d, dy, sp, out):
+                    self._rows_dgrad(d, dy, wpack_d, out)
+            else:
+                out = torch.empty(N, d.Ho, d.Wo, ci, device=dev, dtype=torch.float32)
+                self._rows_dgrad(d, dy, wpack_d, out)
+                if self.up == 2:
+                    dv, out = out, torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
+                    lib.call("dcs_upsample2_grad", _p(dv), _p(out), N, H, W, ci, _stream())
         if addend is not None:
             lib.call("dcs_scale_add", _p(out), _p(addend), 1.0, out.numel(), _stream())
+        return out
+
+    def _dgrad_reflect(self, d, dy, wpack_d, H, W, ci, addend):
+        """The data gradient of a reflect-padded stride-1 conv (d on the padded grid) plus ``addend``: on the
+        ring window kernel, with the fold in the conv epilogue, or as the padded pass + dcs_reflect_fold."""
+        N, Ho, Wo, _ = dy.shape
+        dev = dy.device
+        p = self.pads[0]
+        h3 = getattr(wpack_d, "_dcs_h3", None)
+        if h3 is not None and ci > 4 and dy.is_contiguous() and lib.query("dcs_conv3_win_ok", ctypes.byref(d), 1):
+            out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
+            ring = torch.empty(lib.query("dcs_conv_dgrad_reflect_ring_size", ctypes.byref(d)) // 4,
+                               device=dev, dtype=torch.float32)
+            with self._probe(N * H * W, ci):
+                lib.call("dcs_conv_dgrad_reflect_win", ctypes.byref(d), _p(dy), _p(wpack_d), _p(h3[0]), _p(h3[1]),
+                         _p(h3[2]), _p(addend), _p(out), _p(ring), _stream())
+            return out
+        if _FUSE_FOLD and addend is None and p == 1 and self.k == 3 and H >= 4 and W >= 4 and ci > 4 \
+                and dy.is_contiguous() and ci % 4 == 0:
+            # interior written by the conv epilogue, the ring folded in after.  With a residual
+            # addend the padded pass + dcs_reflect_fold stays faster: the addend read in the
+            # epilogue sits after the MFMA loop (+145 us per 16-image launch against +125 us for
+            # the whole fold pass, profiles/r02e_kernel_table.md)
+            ring = lib.query("dcs_conv_dgrad_reflect_ring_size", ctypes.byref(d)) // 4
+            buf = torch.empty(N * H * W * ci + ring, device=dev, dtype=torch.float32)
+            out = buf[:N * H * W * ci].view(N, H, W, ci)
+            with self._probe(N * Ho * Wo, ci):
+                lib.call("dcs_conv_dgrad_reflect", ctypes.byref(d), _p(dy), _p(wpack_d), None, _p(out),
+                         ctypes.c_void_p(buf.data_ptr() + N * H * W * ci * 4), _stream())
+            return out
+        dpad = torch.empty(N, d.Ho, d.Wo, ci, device=dev, dtype=torch.float32)
+        with self._probe(N * Ho * Wo, ci):
+            self._rows_dgrad(d, dy, wpack_d, dpad)
+        out = torch.empty(N, H, W, ci, device=dev, dtype=torch.float32)
+        lib.call("dcs_reflect_fold", _p(dpad), _p(addend), _p(out), N, H, W, ci, p, _stream())
         return out
 
     def _phase_dgrad_inbwd(self, dy, wpack_d, H, W, inbwd):
@@ -977,31 +935,14 @@ class ConvGeom:
         sp = getattr(wpack_d, "_dcs_sp", None)
         if sp is None or not dy.is_contiguous() or not (self.subpixel or self.stride == 2):
             return None
-        N, Ho, Wo, Co = dy.shape
-        d = lib.ConvDesc()
-        d.N, d.Hs, d.Ws, d.Cs = N, Ho, Wo, Co
-        d.s_n, d.s_c, d.s_h, d.s_w = Ho * Wo * Co, 1, Wo * Co, Co
-        d.csplit = Co
-        d.up, d.pad_mode = 1, DCS_PAD_ZERO
-        d.ldb, d.pro_act, d.epi_act = wpack_d.shape[1], ACT_NONE, ACT_NONE
-        d.mma = _fallback() if _h3() else _MMA
-        _set_mma(d, dy, None, _wrng(wpack_d), wpack_d)
-        d.korder = lib.KORDER_TAP
-        d.Co = self.cin
-        if self.subpixel:
-            d.KH = d.KW = 4
-            d.stride, d.parity, d.pt, d.pl = 2, 0, 1, 1
-        else:
-            d.KH = d.KW = self.k
-            d.stride, d.parity, d.pt, d.pl = 2, 1, self.pads[0], self.pads[1]
-        d.Ho, d.Wo = H, W
+        d = self._desc_dgrad(dy, wpack_d, self.cin, H, W)
         self._phase_mma(d)
         sub = 1 if self.subpixel else 0
         nb = lib.query("dcs_phase_win_dgrad_inbwd_parts_size", ctypes.byref(d), sub)
         if nb == 0:
             return None
         y, st, act = inbwd
-        out = torch.empty(N, H, W, self.cin, device=dy.device, dtype=torch.float32)
+        out = torch.empty(dy.shape[0], H, W, self.cin, device=dy.device, dtype=torch.float32)
         parts = torch.empty(nb // 4, device=dy.device, dtype=torch.float32)
         nchunk = ctypes.c_int(0)
         lib.call("dcs_phase_win_dgrad_inbwd", ctypes.byref(d), sub, _p(dy), _p(sp[0]), _p(sp[1]), _p(sp[2]), _p(out),
@@ -1009,41 +950,28 @@ class ConvGeom:
         return out, parts, nchunk.value
 
     def _dgrad_inbwd(self, dy, wpack_d, H, W, inbwd):
+        """The residual convs' data gradient on the ring window kernel with the IN-backward partial sums of
+        its output fused (dcs_conv_dgrad_reflect_win_inbwd); None where it does not apply."""
         h3 = getattr(wpack_d, "_dcs_h3", None)
         if h3 is None or not dy.is_contiguous() or self.pad_mode != DCS_PAD_REFLECT or self.pads != (1, 1, 1, 1):
             return None
-        N, Ho, Wo, Co = dy.shape
-        d = lib.ConvDesc()
-        d.N, d.Hs, d.Ws, d.Cs = N, Ho, Wo, Co
-        d.s_n, d.s_c, d.s_h, d.s_w = Ho * Wo * Co, 1, Wo * Co, Co
-        d.csplit = Co
-        d.up, d.pad_mode = 1, DCS_PAD_ZERO
-        d.KH = d.KW = self.k
-        d.ldb, d.pro_act, d.epi_act = wpack_d.shape[1], ACT_NONE, ACT_NONE
-        d.mma = _fallback() if _h3() else _MMA
-        _set_mma(d, dy, None, _wrng(wpack_d))
-        d.korder = lib.KORDER_SLICE if self.kslice else lib.KORDER_TAP
-        d.Co = self.cin
-        d.stride, d.parity = 1, 0
-        d.pt = d.pl = self.k - 1
-        d.Ho, d.Wo = H + 2, W + 2
+        d = self._desc_dgrad(dy, wpack_d, self.cin, H, W)
         if not lib.query("dcs_conv3_win_ok", ctypes.byref(d), 1):
             return None
         nb = lib.query("dcs_conv_dgrad_reflect_win_inbwd_parts_size", ctypes.byref(d))
         if nb == 0:
             return None
         y, st, act = inbwd
-        dev = dy.device
+        N, dev = dy.shape[0], dy.device
         out = torch.empty(N, H, W, self.cin, device=dev, dtype=torch.float32)
         ring = torch.empty(lib.query("dcs_conv_dgrad_reflect_ring_size", ctypes.byref(d)) // 4, device=dev,
                            dtype=torch.float32)
         parts = torch.empty(nb // 4, device=dev, dtype=torch.float32)
         nchunk = ctypes.c_int(0)
-        e0 = PROBE.begin() if _is_res_geom(self) else None
-        lib.call("dcs_conv_dgrad_reflect_win_inbwd", ctypes.byref(d), _p(dy), _p(wpack_d), _p(h3[0]), _p(h3[1]),
-                 _p(h3[2]), _p(out), _p(ring), _p(y), _p(st.scale), _p(st.shift), act, _p(parts), nb,
-                 ctypes.byref(nchunk), _stream())
-        PROBE.end(e0, 2.0 * N * H * W * self.cout * self.cin * self.k * self.k)
+        with self._probe(N * H * W, self.cin):
+            lib.call("dcs_conv_dgrad_reflect_win_inbwd", ctypes.byref(d), _p(dy), _p(wpack_d), _p(h3[0]), _p(h3[1]),
+                     _p(h3[2]), _p(out), _p(ring), _p(y), _p(st.scale), _p(st.shift), act, _p(parts), nb,
+                     ctypes.byref(nchunk), _stream())
         return out, parts, nchunk.value
 
     # ---- weight gradient ---------------------------------------------------------------
@@ -1054,15 +982,14 @@ class ConvGeom:
         _check_dev(dy, s.t, s.t2)
         pro_act = pro[2] if pro is not None else ACT_NONE
         d = self._desc_fwd(s, 0, pro_act, ACT_NONE, rows=not self.narrow)
-        if self.narrow and _HEAD_PROJ and pro is not None and pro_max is not None and _h3() and s.t2 is None \
-                and dy.is_contiguous():
+        if self.narrow and pro is not None and pro_max is not None and _h3() and s.t2 is None and dy.is_contiguous():
             m0, d.mma = d.mma, _fixed_mma("head")
             if lib.query("dcs_head_fwd_proj_ok", ctypes.byref(d)):
                 if out is None:
                     out = torch.empty(self.cout, self.cin, self.k, self.k, device=dy.device, dtype=torch.float32)
                 ws = workspace(lib.query("dcs_head_wgrad_proj_workspace_size", ctypes.byref(d)), dy.device)
-                lib.call("dcs_head_wgrad_proj", ctypes.byref(d), _p(dy), _p(s.t), _p(pro[0]), _p(pro[1]),
-                         _p(pro_max), _p(out), _p(ws), ws.numel(), _stream())
+                lib.call("dcs_head_wgrad_proj", ctypes.byref(d), _p(dy), _p(s.t), *_pro_ptrs(pro), _p(pro_max), _p(out),
+                         _p(ws), ws.numel(), _stream())
                 return out
             d.mma = m0
         if not self.narrow and s.t2 is None and _h3() and s.t.is_contiguous():
@@ -1078,18 +1005,10 @@ class ConvGeom:
             d.mma = _fixed_mma("stem_wgrad")
             lib.call("dcs_stem_wgrad", ctypes.byref(d), _p(dy), _p(s.t), _p(out), _p(ws), ws.numel(), _stream())
             return out
-        if self.narrow:
-            nb = lib.query("dcs_conv_wgrad_narrow_workspace_size", ctypes.byref(d))
-            ws = workspace(nb, dy.device)
-            lib.call("dcs_conv_wgrad_narrow", ctypes.byref(d), _p(dy), _p(s.t), _p(s.t2),
-                     _p(pro[0]) if pro else None, _p(pro[1]) if pro else None, _p(out), _p(ws),
-                     ws.numel(), _stream())
-        else:
-            nb = lib.query("dcs_conv_wgrad_workspace_size", ctypes.byref(d))
-            ws = workspace(nb, dy.device)
-            lib.call("dcs_conv_wgrad", ctypes.byref(d), _p(dy), _p(s.t), _p(s.t2),
-                     _p(pro[0]) if pro else None, _p(pro[1]) if pro else None, _p(out), _p(ws),
-                     ws.numel(), _stream())
+        api = "dcs_conv_wgrad_narrow" if self.narrow else "dcs_conv_wgrad"
+        ws = workspace(lib.query(api + "_workspace_size", ctypes.byref(d)), dy.device)
+        lib.call(api, ctypes.byref(d), _p(dy), _p(s.t), _p(s.t2), *_pro_ptrs(pro), _p(out), _p(ws), ws.numel(),
+                 _stream())
         return out
 
 
@@ -1116,19 +1035,30 @@ def pack_nhwc4(x: torch.Tensor, x2: Optional[torch.Tensor] = None) -> torch.Tens
     return out
 
 
+def _in_alloc(N: int, C: int, device, want_max: bool) -> INStats:
+    scale = torch.empty(N, C, device=device, dtype=torch.float32)
+    shift = torch.empty(N, C, device=device, dtype=torch.float32)
+    xmax = torch.empty(N, C, device=device, dtype=torch.float32) if want_max else None
+    xam = torch.empty(N, C, device=device, dtype=torch.int32) if want_max else None
+    return INStats(scale, shift, xmax, xam)
+
+
+def _in_finish(parts: torch.Tensor, nchunk: int, N: int, C: int, device, want_max: bool) -> INStats:
+    """The IN statistics from the ``nchunk`` per-tile partials a conv epilogue left in ``parts``."""
+    st = _in_alloc(N, C, device, want_max)
+    lib.call("dcs_in_stats_finish", _p(parts), N, C, nchunk, IN_EPS, _p(st.scale), _p(st.shift), _p(st.xmax),
+             _p(st.xargmax), _stream())
+    return st
+
+
 def in_stats(x: torch.Tensor, want_max: bool = False) -> INStats:
     _check_dev(x)
     N, H, W, C = x.shape
-    dev = x.device
-    scale = torch.empty(N, C, device=dev, dtype=torch.float32)
-    shift = torch.empty(N, C, device=dev, dtype=torch.float32)
-    xmax = torch.empty(N, C, device=dev, dtype=torch.float32) if want_max else None
-    xam = torch.empty(N, C, device=dev, dtype=torch.int32) if want_max else None
-    nb = lib.query("dcs_in_stats_workspace_size", N, H * W, C)
-    ws = workspace(nb, dev)
-    lib.call("dcs_in_stats", _p(x), N, H * W, C, IN_EPS, _p(scale), _p(shift), _p(xmax), _p(xam),
+    st = _in_alloc(N, C, x.device, want_max)
+    ws = workspace(lib.query("dcs_in_stats_workspace_size", N, H * W, C), x.device)
+    lib.call("dcs_in_stats", _p(x), N, H * W, C, IN_EPS, _p(st.scale), _p(st.shift), _p(st.xmax), _p(st.xargmax),
              _p(ws), ws.numel(), _stream())
-    return INStats(scale, shift, xmax, xam)
+    return st
 
 
 def in_apply(x: torch.Tensor, st: INStats, act: int) -> torch.Tensor:
@@ -1154,7 +1084,7 @@ def head_dgrad_in(dy_out: torch.Tensor, wk: torch.Tensor, y: torch.Tensor, st: I
     the IN backward's two passes (dcs_head_dgrad_in).  ``wk``: the head's dgrad pack (K-major
     [49 * 64][1]).  None where it does not apply (other modes, act, or images below 8 x 8)."""
     N, H, W, C = y.shape
-    if not (_HEAD_PROJ and _h3() and C == 64 and act == ACT_RELU and H >= 8 and W >= 8 and y.is_contiguous()
+    if not (_h3() and C == 64 and act == ACT_RELU and H >= 8 and W >= 8 and y.is_contiguous()
             and dy_out.numel() == N * H * W and wk.numel() == 49 * 64):
         return None
     _check_dev(dy_out, wk, y)
@@ -1382,8 +1312,8 @@ def gen_loss_fused(jobs, recipe=None, extra=(), ssim_data_range=1.0, ca=(0.15, 1
             if t is not None:
                 assert t.is_contiguous() and t.shape == p.shape, key
         a = arr[k]
-        a.pred, a.target, a.source = p.data_ptr(), _ptr(j.get("target")), _ptr(j.get("source"))
-        a.add0, a.add1, a.grad = _ptr(j.get("add0")), _ptr(j.get("add1")), _ptr(j.get("grad"))
+        a.pred, a.target, a.source = _p(p), _p(j.get("target")), _p(j.get("source"))
+        a.add0, a.add1, a.grad = _p(j.get("add0")), _p(j.get("add1")), _p(j.get("grad"))
         a.n_img, a.H, a.W, a.flags = p.shape[0], p.shape[2], p.shape[3], int(j["flags"])
         for key in ("c_l1", "c_grad", "c_ssim", "c_ca", "c_mse", "t_const", "c_add0", "c_add1"):
             setattr(a, key, float(j.get(key, 0.0)))
@@ -1396,7 +1326,7 @@ def gen_loss_fused(jobs, recipe=None, extra=(), ssim_data_range=1.0, ca=(0.15, 1
         bias = (ctypes.c_float * nout)(*b)
         coef = (ctypes.c_float * (nout * 5 * len(jobs)))(*[float(v) for row in c for v in row])
         coefx = (ctypes.c_float * (nout * 4))(*[float(v) for row in cx for v in row])
-        ex = (ctypes.c_void_p * 4)(*[_ptr(e) for e in (list(extra) + [None] * 4)[:4]])
+        ex = (ctypes.c_void_p * 4)(*[_p(e) for e in (list(extra) + [None] * 4)[:4]])
         out = torch.empty(nout, device=dev, dtype=torch.float32)
     lib.call("dcs_gen_loss_fused", arr, len(jobs), float(ssim_data_range), float(ca[0]), float(ca[1]), float(ca[2]),
              bias, coef, coefx, ex, nout, _p(out), _p(ws), ws.numel(), _stream())

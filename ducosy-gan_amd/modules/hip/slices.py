@@ -8,7 +8,6 @@ raises, kernels go to the current stream, ``with torch.cuda.device(...)`` is lef
 """
 from __future__ import annotations
 
-import ctypes
 from functools import lru_cache
 from typing import Optional, Tuple
 
@@ -16,17 +15,10 @@ import numpy as np
 import torch
 
 from . import lib
+from .lib import ptr as _p, stream as _stream
 
 MAX_TAPS = lib.RESIZE_MAX_TAPS
 MAX_RATIO = 8  # in/out above this needs more than MAX_TAPS taps
-
-
-def _p(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 @lru_cache(maxsize=64)

@@ -13,18 +13,11 @@ import numpy as np
 import torch
 
 from . import lib
+from .lib import ptr as _p, stream as _stream
 
 MAX_RADIUS = lib.VOL_MAX_RADIUS
 MAX_MEDIAN = lib.VOL_MAX_MEDIAN
 _FDT = {torch.float32: lib.VOL_F32, torch.float64: lib.VOL_F64}
-
-
-def _p(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _vol(t: torch.Tensor, name: str, dtypes) -> torch.Tensor:
