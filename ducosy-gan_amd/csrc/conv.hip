@@ -210,40 +210,10 @@ struct RowInfo {
     long long out_off;    // element offset of the output pixel (channel 0), -1 if invalid
 };
 
-// fold (conv_rows_kernel of dcs_conv_dgrad_reflect only): see the fold branches below
-__device__ __forceinline__ RowInfo row_info(const dcs_conv_desc& d, const ClassGeom& g, int m, int fold = 0) {
+// fold (conv_rows_kernel of dcs_conv_dgrad_reflect only): see the fold branch below
+__device__ __forceinline__ RowInfo row_info(const dcs_conv_desc& d, const ClassGeom& g, int m, bool fold = false) {
     // 32-bit index math: the host guarantees N*My*Mx < 2^31
     RowInfo r;
-    if (fold == 2) {
-        // the one-pixel ring of the (H+2) x (W+2) padded grid only (dcs_conv_dgrad_reflect_win: the
-        // interior comes from the window kernel), rows in the ring buffer's order: top row, bottom
-        // row, then (left, right) of rows 1..H; out_off indexes the ring buffer
-        // The rows are enumerated segment by segment over the whole batch (every image's top row,
-        // then every bottom row, left column, right column), so a 128-row tile lies in one segment
-        // and reads only that segment's kernel row / column of taps (ring_tap_mask)
-        const int H = d.Ho - 2, ringlen = 2 * d.Wo + 2 * H;
-        if (m >= ringlen * d.N) { r.n = 0; r.by = -100000; r.bx = -100000; r.out_off = -1; return r; }
-        int n, idx, oy, ox;
-        const int sw = d.N * d.Wo, sh = d.N * H;
-        if (m < 2 * sw) {  // top / bottom rows
-            const int u = m < sw ? m : m - sw;
-            n = u / d.Wo;
-            ox = u - n * d.Wo;
-            oy = m < sw ? 0 : d.Ho - 1;
-            idx = (m < sw ? 0 : d.Wo) + ox;
-        } else {           // left / right columns of rows 1 .. H
-            const int v = m - 2 * sw, right = v >= sh ? 1 : 0, u = right ? v - sh : v;
-            n = u / H;
-            oy = 1 + (u - n * H);
-            ox = right ? d.Wo - 1 : 0;
-            idx = 2 * d.Wo + 2 * (oy - 1) + right;
-        }
-        r.n = n;
-        r.by = oy * d.stride - d.pt;
-        r.bx = ox * d.stride - d.pl;
-        r.out_off = ((long long)n * ringlen + idx) * d.Co;
-        return r;
-    }
     const int per = g.My * g.Mx;
     if (m >= per * d.N) { r.n = 0; r.by = -100000; r.bx = -100000; r.out_off = -1; return r; }
     const int n = m / per;
@@ -663,12 +633,9 @@ template <int BM, int BN, int VEC, int TAG, int MMA = MMA_F32>
 __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || MMA == MMA_F16) ? (BM == 256 ? 2 : X6_OCC) : 2) void conv_rows_kernel(
     const dcs_conv_desc din, const float* __restrict__ src, const float* __restrict__ src2,
     const float* __restrict__ wp, const float* __restrict__ bias, const float* __restrict__ psc,
-    const float* __restrict__ psh, float* __restrict__ out_, int gx, int gy, Part* __restrict__ parts, int fold_) {
+    const float* __restrict__ psh, float* __restrict__ out, int gx, int gy, Part* __restrict__ parts, int fold) {
     const dcs_conv_desc d = specialise<TAG>(din);
-    // fold_ = mode (bits 0-1: 0 none, 1 interior + ring, 2 ring rows only) | K splits << 2 (ring rows:
-    // the grid's z index is the split, each split writes its own copy of the ring, summed by the fold)
-    const int fold = fold_ & 3;
-    const int ksplit = (fold_ >> 2) > 1 ? (fold_ >> 2) : 1;
+    // fold (dcs_conv_dgrad_reflect): the padded grid's interior goes to the unpadded tensor, its ring behind it
     static_assert(BM == 128 || (BM == 256 && (MMA == MMA_BF16X6 || MMA == MMA_BF16P || MMA == MMA_F16X3 || MMA == MMA_F16) && BN == 128 && VEC == 1),
                   "A loader: 2 threads per row; 256-row tiles only for the x6 128-column kernel");
     constexpr int NTH = 2 * BM;                    // threads (two per A row)
@@ -729,11 +696,9 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
     const int ntile = L % gy;
     const int rest = L / gy;
     const int mtile = rest % gx;
-    const int z = ksplit > 1 ? 0 : rest / gx;
-    const int ks = ksplit > 1 ? rest / gx : 0;
+    const int z = rest / gx;
     const ClassGeom g = class_geom(d, z);
-    const long long M = fold == 2 ? (long long)d.N * (2 * d.Wo + 2 * (d.Ho - 2)) : (long long)g.My * g.Mx * d.N;
-    float* __restrict__ const out = out_ + (long long)ks * M * d.Co;
+    const long long M = (long long)g.My * g.Mx * d.N;
     const long long m0 = (long long)mtile * BM;
     if (m0 >= M) return;
     const int n0 = ntile * BN;
@@ -766,32 +731,8 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
     const int brow = tid / BTPR, bkq = (tid % BTPR) * ((MMA == MMA_BF16P || NSUB > 1) ? 16 / BTPR : BKPT);
     const float* bsrc = wp + (long long)(n0 + brow) * d.ldb;
 
-    // taps this tile needs (ring rows of a padded-grid data gradient, TAG 1 fold 2: a segment of the ring
-    // reads one kernel row or column; every other launch: all taps)
-    int tapmask = (1 << g.ntaps) - 1, ntap_act = g.ntaps;
-    if constexpr (TAG == 1 && H3) {
-        if (fold == 2) {
-            const int Hr = d.Ho - 2, sw = d.N * d.Wo, sh = d.N * Hr;
-            auto seg_mask = [&](long long m) {  // (ty, tx) bit ty * 3 + tx of the taps segment m's rows read
-                return m < sw ? 0x1C0 : (m < 2 * sw ? 0x007 : (m < 2 * sw + sh ? 0x124 : 0x049));
-            };
-            const long long mlast = (m0 + BM < M ? m0 + BM : M) - 1;
-            int msk = 0;
-            for (int sgi = 0; sgi < 4; ++sgi) {  // the segments between the tile's first and last row
-                const long long sb = sgi == 0 ? 0 : (sgi == 1 ? sw : (sgi == 2 ? 2 * sw : 2 * sw + sh));
-                const long long se = sgi == 0 ? sw : (sgi == 1 ? 2 * sw : (sgi == 2 ? 2 * sw + sh : 2 * sw + 2 * sh));
-                if (sb <= mlast && se > m0) msk |= seg_mask(sb);
-            }
-            tapmask = __builtin_amdgcn_readfirstlane(msk);
-            ntap_act = __builtin_popcount(tapmask);
-        }
-    }
-    const int K = ntap_act * d.Cs;
-    const int nkt_all = (K + BKT - 1) / BKT;
-    const int kper = (nkt_all + ksplit - 1) / ksplit;
-    const int kt_beg = ks * kper;                                         // this split's k-tiles
-    const int nkt = kt_beg + kper < nkt_all ? kt_beg + kper : nkt_all;  // (exclusive end)
-    const int kb0 = kt_beg * BKT;
+    const int K = g.ntaps * d.Cs;
+    const int nkt = (K + BKT - 1) / BKT;
     const int Hv = d.Hs * d.up, Wv = d.Ws * d.up;
     const float* srow = src + ri.n * d.s_n;
     const long long so = (long long)ri.n * d.Cs;
@@ -835,21 +776,21 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
     constexpr bool KS = TAG == 1 || KSB;
     int aj, ac;
     if constexpr (KS) {
-        const int p0 = (kb0 + akq) >> 4;
+        const int p0 = akq >> 4;
         aj = p0 % g.ntaps;
         ac = (p0 / g.ntaps) * 16 + (akq & 15);
     } else {
-        aj = (kb0 + akq) / d.Cs;
-        ac = (kb0 + akq) - ((kb0 + akq) / d.Cs) * d.Cs;
+        aj = akq / d.Cs;
+        ac = akq - (akq / d.Cs) * d.Cs;
     }
     int bj, bc;
     if constexpr (KSB) {
-        const int p0 = (kb0 + bkq) >> 4;
+        const int p0 = bkq >> 4;
         bj = p0 % g.ntaps;
         bc = (p0 / g.ntaps) * 16 + (bkq & 15);
     } else {
-        bj = (kb0 + bkq) / d.Cs;
-        bc = (kb0 + bkq) - ((kb0 + bkq) / d.Cs) * d.Cs;
+        bj = bkq / d.Cs;
+        bc = bkq - (bkq / d.Cs) * d.Cs;
     }
     auto advance = [&](int& j, int& c) {
         if constexpr (KS) {
@@ -878,35 +819,12 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
     struct Walk {
         int ty, tx, cs;  // tap position within the class, first channel of the slice
     };
-    auto walk_init = [&](int p0) {  // p0: index of the first 16-k step (uniform)
-        Walk w;
-        int j = p0 % ntap_act;
-        if constexpr (TAG == 1 && H3) {  // the j-th tap of the mask
-            int t = 0;
-            for (int q = 0; q < g.ntaps; ++q)
-                if ((tapmask >> q) & 1) {
-                    if (j == 0) { t = q; break; }
-                    --j;
-                }
-            j = t;
-        }
-        w.cs = __builtin_amdgcn_readfirstlane((p0 / ntap_act) * 16);
-        w.ty = __builtin_amdgcn_readfirstlane(j / wntx);
-        w.tx = __builtin_amdgcn_readfirstlane(j - (j / wntx) * wntx);
-        return w;
-    };
-    auto walk_step1 = [&](Walk& w) {
+    auto walk_step = [&](Walk& w) {
         const bool wx = w.tx + 1 == wntx;
         const bool wy = wx && w.ty + 1 == wnty;
         w.tx = wx ? 0 : w.tx + 1;
         w.ty = wy ? 0 : (wx ? w.ty + 1 : w.ty);
         w.cs += wy ? 16 : 0;
-    };
-    auto walk_step = [&](Walk& w) {
-        walk_step1(w);
-        if constexpr (TAG == 1 && H3) {  // skip the taps outside the mask (uniform; a no-op for a full mask)
-            while (!((tapmask >> (w.ty * wntx + w.tx)) & 1)) walk_step1(w);
-        }
     };
     // (ady, adx): source offset of the tap; bt: its column block in the packed weights (tap_decode).
     // All three are affine in (ty, tx) with per-class constants (parity 1: ady = (ry + pt - ty0) / 2
@@ -926,7 +844,7 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
         bt = wb0 + wbty * w.ty + wbtx * w.tx;
     };
     constexpr bool UWALK = KS;
-    Walk wa = walk_init(kb0 >> 4), wb = wa;
+    Walk wa{0, 0, 0}, wb = wa;  // the first tap of the first slice
     const int alo = akq & 15, blo = bkq & 15;
     // linear gather (zero padding, no upsampling): the lane's element offset of tap (0, 0) at channel
     // alo of the slice; a tap adds ady * s_h + adx * s_w + slice base (uniform)
@@ -1348,8 +1266,8 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
             for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; t[i][j][r] = 0.f; }
 
     int pa0[NSUB], pa1[NSUB];
-    load_a(kt_beg, ra, pa0);
-    load_b(kt_beg, rb);
+    load_a(0, ra, pa0);
+    load_b(0, rb);
     store_tiles(0, ra, rb, pa0);
     __syncthreads();
 
@@ -1474,9 +1392,9 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
             // assume it may be missing and wait for every load at the next LDS store.
             float4 ra2[ACH], rb2[BCH];
             int pa2[NSUB];
-            load_a(kt_beg + 1, ra, pa1);
-            load_b(kt_beg + 1, rb);
-            for (int kt = kt_beg; kt < nkt; kt += 2) {
+            load_a(1, ra, pa1);
+            load_b(1, rb);
+            for (int kt = 0; kt < nkt; kt += 2) {
                 load_a(kt + 2, ra2, pa2);
                 load_b(kt + 2, rb2);
                 step(0, 0);
@@ -1498,8 +1416,8 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
                 __syncthreads();
             }
         } else {
-            for (int kt = kt_beg; kt < nkt; ++kt) {
-                const int cur = (kt - kt_beg) & 1;
+            for (int kt = 0; kt < nkt; ++kt) {
+                const int cur = kt & 1;
 #pragma unroll
                 for (int st = 0; st < NST / 2; ++st) step(cur, st);
                 if (kt + 1 < nkt) { load_a(kt + 1, ra, pa1); load_b(kt + 1, rb); }
@@ -1511,8 +1429,8 @@ __global__ __launch_bounds__(2 * BM, (MMA == MMA_BF16X6 || MMA == MMA_F16X3 || M
             }
         }
     } else
-    for (int kt = kt_beg; kt < nkt; ++kt) {
-        const int cur = (kt - kt_beg) & 1;
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int cur = kt & 1;
         float4 af[IM][4], bf[JN][4];
 #pragma unroll
         for (int i = 0; i < IM; ++i)
@@ -2383,26 +2301,10 @@ extern "C" int dcs_pack_batch(const dcs_pack_job* jobs_dev, int njobs, int g1, i
 }
 
 namespace dcs {
+// fold: dcs_conv_dgrad_reflect's output mapping (the padded grid's interior into out, its ring behind it)
 int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2, const float* wpack, const float* bias,
                    const float* psc, const float* psh, float* out, Part* parts, int* bm_used, void* stream,
-                   int fold = 0);
-// K splits of the ring-rows pass (fold 2) of a padded-grid data gradient: enough workgroups for two
-// per CU, at least 4 k-tiles per split, at most 8 ring copies
-int ring_ksplit(const dcs_conv_desc& d) {
-    const long long M = (long long)d.N * (2 * d.Wo + 2 * (d.Ho - 2));
-    const long long tiles = cdiv(M, 128) * cdiv(d.Co, d.Co > 64 ? 128 : 64);
-    // a ring segment reads one kernel row or column (the masked walk of conv_rows_kernel, fold 2)
-    const long long nkt = cdiv((long long)(d.KH > d.KW ? d.KH : d.KW) * d.Cs, 32);
-    long long k = cdiv(512, tiles);
-    if (k > 8) k = 8;
-    while (k > 1 && nkt / k < 8) --k;
-    return k < 1 ? 1 : (int)k;
-}
-}  // namespace dcs
-namespace dcs {
-int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2, const float* wpack, const float* bias,
-                   const float* psc, const float* psh, float* out, Part* parts, int* bm_used, void* stream,
-                   int fold) {
+                   bool fold = false) {
     int e = validate(dp, true);
     if (e) return e;
     const dcs_conv_desc& d = *dp;
@@ -2420,13 +2322,8 @@ int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2,
         long long M = (long long)g.My * g.Mx * d.N;
         if (M > Mmax) Mmax = M;
     }
-    if (fold == 2) Mmax = (long long)d.N * (2 * d.Wo + 2 * (d.Ho - 2));  // ring rows only
     const int gx = (int)cdiv(Mmax, 128), gy = (int)cdiv(d.Co, BN);
-    // ring rows (fold 2): K split over the grid's z so the few ring tiles fill the chip (each split
-    // writes its own ring copy; reflect_ring_fold sums them)
-    const int ksplit = fold == 2 ? ring_ksplit(d) : 1;
-    const int fold_arg = fold | (ksplit > 1 ? ksplit << 2 : 0);
-    dim3 grid((unsigned)(gx * gy * ncls * ksplit));
+    dim3 grid((unsigned)(gx * gy * ncls));
     if (bm_used) *bm_used = 128;
     const bool vec = vec_ok(dp, src);
     const bool v4 = !vec && vec4_ok(dp, src) && d.pro_act == DCS_ACT_NONE && !d.parity;
@@ -2448,13 +2345,13 @@ int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2,
 #define DCS_ROWS_X6F(BM_, BN_, VEC_, TAG_, G)                                                                          \
     if (d.mma == MMA_F16X3)                                                                                          \
         hipLaunchKernelGGL((conv_rows_kernel<BM_, BN_, VEC_, TAG_, MMA_F16X3>), G, dim3(2 * BM_), 0, s, d, src, src2, \
-                           wpack, bias, psc, psh, out, gxx, gy, parts, fold_arg);                                        \
+                           wpack, bias, psc, psh, out, gxx, gy, parts, fold);                                            \
     else if (d.mma == MMA_F16)                                                                                       \
         hipLaunchKernelGGL((conv_rows_kernel<BM_, BN_, VEC_, TAG_, MMA_F16>), G, dim3(2 * BM_), 0, s, d, src, src2,   \
-                           wpack, bias, psc, psh, out, gxx, gy, parts, fold_arg);                                        \
+                           wpack, bias, psc, psh, out, gxx, gy, parts, fold);                                            \
     else                                                                                                             \
         hipLaunchKernelGGL((conv_rows_kernel<BM_, BN_, VEC_, TAG_, MMA_BF16X6>), G, dim3(2 * BM_), 0, s, d, src, src2, \
-                           wpack, bias, psc, psh, out, gxx, gy, parts, fold_arg);
+                           wpack, bias, psc, psh, out, gxx, gy, parts, fold);
     if (vec && x6f) {  // x6 / f16x3: 128- or 64-column tiles
         // 256-row tiles where they divide the pixels evenly (the forward over whole 128 x 128
         // images); the 130 x 130 padded data gradient keeps 128-row tiles (measured: its partial
@@ -2492,33 +2389,33 @@ int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2,
         if (Mmax % 256 == 0 && (!parts || ((long long)d.Ho * d.Wo) % 256 == 0)) {
             const int gx2 = (int)cdiv(Mmax, 256);
             hipLaunchKernelGGL((conv_rows_kernel<256, 128, 1, 1, MMA_BF16P>), dim3((unsigned)(gx2 * gy)), dim3(512), 0, s,
-                               d, src, src2, wpack, bias, psc, psh, out, gx2, gy, parts, fold_arg);
+                               d, src, src2, wpack, bias, psc, psh, out, gx2, gy, parts, fold);
             if (bm_used) *bm_used = 256;
         } else {
             hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 1, MMA_BF16P>), grid, dim3(NT), 0, s, d, src, src2, wpack,
-                               bias, psc, psh, out, gx, gy, parts, fold_arg);
+                               bias, psc, psh, out, gx, gy, parts, fold);
         }
         return check_launch("conv_rows");
     }
     const bool mma_ok = vec && (d.mma == MMA_BF16X3 || (d.mma == MMA_BF16 && d.Cs % 64 == 0 && d.ldb % 64 == 0));
     if (mma_ok) {  // bf16 operand modes (vectorised gathers; else exact f32)
 #define DCS_ROWS_MMA(M)                                                                                              \
-    if (BN == 128 && res) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 1, M>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg); \
-    else if (BN == 128) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 0, M>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);  \
-    else hipLaunchKernelGGL((conv_rows_kernel<128, 64, 1, 0, M>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
+    if (BN == 128 && res) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 1, M>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);     \
+    else if (BN == 128) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 0, M>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);      \
+    else hipLaunchKernelGGL((conv_rows_kernel<128, 64, 1, 0, M>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
         if (d.mma == MMA_BF16) { DCS_ROWS_MMA(MMA_BF16) } else { DCS_ROWS_MMA(MMA_BF16X3) }
 #undef DCS_ROWS_MMA
         return check_launch("conv_rows");
     }
     if (BN == 128) {
-        if (vec && res) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 1>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
-        else if (vec) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
-        else if (v4) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 2, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
-        else hipLaunchKernelGGL((conv_rows_kernel<128, 128, 0, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
+        if (vec && res) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 1>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
+        else if (vec) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 1, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
+        else if (v4) hipLaunchKernelGGL((conv_rows_kernel<128, 128, 2, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
+        else hipLaunchKernelGGL((conv_rows_kernel<128, 128, 0, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
     } else {
-        if (vec) hipLaunchKernelGGL((conv_rows_kernel<128, 64, 1, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
-        else if (v4) hipLaunchKernelGGL((conv_rows_kernel<128, 64, 2, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
-        else hipLaunchKernelGGL((conv_rows_kernel<128, 64, 0, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold_arg);
+        if (vec) hipLaunchKernelGGL((conv_rows_kernel<128, 64, 1, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
+        else if (v4) hipLaunchKernelGGL((conv_rows_kernel<128, 64, 2, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
+        else hipLaunchKernelGGL((conv_rows_kernel<128, 64, 0, 0>), grid, dim3(NT), 0, s, d, src, src2, wpack, bias, psc, psh, out, gx, gy, parts, fold);
     }
     return check_launch("conv_rows");
 }
@@ -3291,9 +3188,8 @@ extern "C" int dcs_reflect_fold(const float* dxpad, const float* addend, float* 
 
 extern "C" size_t dcs_conv_dgrad_reflect_ring_size(const dcs_conv_desc* dp) {
     if (!dp || dp->Ho < 6 || dp->Wo < 6) return 0;
-    // the window path's ring pass writes one ring copy per K split
-    const int copies = ring_ksplit(*dp) > RG_COPIES ? ring_ksplit(*dp) : RG_COPIES;  // (conv_win.hip's ring16_kernel)
-    return (size_t)copies * dp->N * (2 * dp->Wo + 2 * (dp->Ho - 2)) * dp->Co * sizeof(float);
+    // the window path's ring pass (conv_win.hip's ring16_kernel) writes RG_COPIES ring copies
+    return (size_t)RG_COPIES * dp->N * (2 * dp->Wo + 2 * (dp->Ho - 2)) * dp->Co * sizeof(float);
 }
 
 extern "C" int dcs_conv_dgrad_reflect(const dcs_conv_desc* dp, const float* dy, const float* wpack,
@@ -3308,7 +3204,7 @@ extern "C" int dcs_conv_dgrad_reflect(const dcs_conv_desc* dp, const float* dy, 
                                    "(Ho = Hs + 2, pt = pl = 2, zero pad, no activations)");
     if (ring != dx + (long long)d.N * (d.Ho - 2) * (d.Wo - 2) * d.Co)
         return fail(DCS_E_INVALID, "conv_dgrad_reflect: ring must directly follow dx (one allocation)");
-    int e = conv_rows_impl(&d, dy, addend, wpack, nullptr, nullptr, nullptr, dx, nullptr, nullptr, stream, 1);
+    int e = conv_rows_impl(&d, dy, addend, wpack, nullptr, nullptr, nullptr, dx, nullptr, nullptr, stream, true);
     if (e) return e;
     const int H = d.Ho - 2, W = d.Wo - 2, C4 = d.Co / 4;
     const long long total = (long long)d.N * (2 * W + 2 * (H - 2)) * C4;

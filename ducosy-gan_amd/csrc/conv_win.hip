@@ -9,14 +9,34 @@
 // slice stages the (R + 2) x (W + 2) source window once (520 pixels at W = 128: 2.0 values per output
 // pixel instead of 9); the nine taps read their MFMA fragments from the window at a per-tap pixel
 // offset.  The weights arrive pre-split (dcs_pack_weights_h3: hi / lo fp16 planes, slice-major K), so
-// their k-tiles are copied to LDS without arithmetic.
+// their k-steps are copied to LDS without arithmetic (LDS-DMA, win_glds).
+// 8 waves = 4 (pixels) x 2 (channels) of 64 x 64; one workgroup per CU.
 //
-// K loop: 16 slices x 3 kernel rows (ty) = 48 k-tiles of 48 k; a k-tile is three 16-k sub-tiles
-// (tx = 0, 1, 2) of 2 x 2 blocks x 3 products (lo*hi, hi*lo, hi*hi) per wave.  One inner fp32
-// accumulation chain per slice (144 k), added to the running sum (two-level, as conv.hip).
-// 8 waves = 4 (pixels) x 2 (channels) of 64 x 64; one workgroup per CU (115 KB of LDS).  The k-tile
-// schedule (LDS-DMA for B, one window unit in flight, fragments read ahead, staggered wave pairs) is
-// described at conv3_win_h3_kernel.
+// The MFMA is v_mfma_f32_16x16x32_f16 (conv3_win16_kernel).  It does the same MACs per fragment byte
+// as the 32x32x16 form, but under the package power limit sustains ~12 % more FLOP/s: 1758 against
+// 1562 TFLOP/s of f16x3 products in a bare LDS-read + MFMA loop with every CU busy on random operands
+// (scripts/probes/mfma_shape_power.hip, profiles/r06b/; MI355X_MICROARCH.md, DVFS item 7).
+//
+// K = 32 per MFMA = two (slice, tap) units of 16 channels: the fragments' k groups 0, 1 (lanes 0-31)
+// take unit 2j, k groups 2, 3 (lanes 32-63) unit 2j + 1 -- the packed B's k = 16 unit + channel, so a
+// k-step is 32 consecutive packed k.  A slice has nine taps: the k-steps walk the 18 units of a PAIR
+// of slices, 9 k-steps, k-step 4 taking tap 8 of the even slice and tap 0 of the odd one.  The even
+// slice of a pair sits in window buffer 0, the odd one in buffer 1; the next odd slice is staged
+// during k-steps 0-3 (buffer 1 is free after the previous pair's k-step 8), the next even slice
+// during k-steps 5-8 (buffer 0 is free after k-step 4), one staging unit in flight per thread: only
+// one unit's eight floats are live at a time.  Only the window's interior columns are loaded (two
+// units per thread); the halo columns are written by the units of source columns 1 and W - 2
+// (reflection) or zeroed once (zero padding).  Waves 4-7 (the partners of waves 0-3 on their SIMDs)
+// store their staging unit at the top of the next k-step instead of after their MFMAs, so the two
+// waves of a SIMD are not in the same phase.
+// One barrier per k-step: B (128 output-channel rows x 32 k x 2 planes, 16 KB) by LDS-DMA into the
+// other of the B buffers.  Per k-step and wave: 4 x 4 blocks of 16 x 16 x 3 products = 48 MFMAs.
+// Row block i of wave wm holds the 16 consecutive tile pixels wm * 64 + 16 i + (lane & 15) (W >= 16:
+// a block never crosses an image row), so the window needs no swizzle: the 16 lanes of a
+// ds_read_b128 lane group read 16 distinct 16-byte bank groups (pixel stride 32 B, the two channel
+// halves on odd / even groups).  A B row (output channel co) holds its four 8-k groups rotated by
+// 2 * ((co >> 2) & 3), which makes the B reads conflict-free too.  Two-level accumulation: chains of
+// 5 and 4 k-steps (160 / 128 k), added to the running sum.
 #include "common.hpp"
 #include "conv_common.hpp"
 #include <type_traits>
@@ -27,9 +47,6 @@ namespace {
 
 constexpr int WIN_BN = 128, WIN_NT = 512;  // tiles: 256 pixels (whole rows) x WIN_BN channels
 constexpr int WIN_PIX = 520;             // window pixels for W <= 128: (256 / W + 2) * (W + 2) <= 520
-// halves per B plane-slot: 128 rows x 16 k + 48 (96 B: the three tx slots of a row, written by
-// neighbouring lanes, land on distinct banks)
-constexpr int WIN_SLOT = 128 * 16 + 48;
 // window staging units (pixel, 8-channel half) per thread: the interior columns only, (256 / W + 2) x W
 // pixels x 2 halves <= 1024 for W <= 128
 constexpr int WIN_UNITS = 2;
@@ -42,25 +59,6 @@ struct WinArgs {
     int rng_n;           // partial maxima of the source range record
 };
 
-typedef short shortx8 __attribute__((ext_vector_type(8)));
-
-// half-element offset of (buffer, plane, window pixel, 8-channel half) in the window region: the
-// pixels of a pair swap on odd groups of 8 pixels and the 16-byte halves of a pixel on odd groups of
-// 16, so the fragment reads (every other pixel from any start: the MFMA row blocks interleave) and the
-// staging writes are both conflict-free
-__device__ __forceinline__ int win_off(int buf, int pl, int wpix, int h) {
-    return ((buf * 2 + pl) * WIN_PIX + (wpix ^ ((wpix >> 3) & 1))) * 16 + 8 * (h ^ ((wpix >> 4) & 1));
-}
-// tile pixel of accumulator element r of row block i (the blocks interleave: block i holds pixels
-// 2m + i of the wave's 64, so block 0 at tap tx + 1 reads the fragment block 1 read at tap tx)
-__device__ __forceinline__ int win_pix(int wm, int i, int r, int kh) {
-    return wm * 64 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * kh) + i;
-}
-// B: (buffer, plane, tx, output-channel row, half)
-__device__ __forceinline__ int wb_off(int buf, int pl, int tx, int row, int h) {
-    return (buf * 6 + pl * 3 + tx) * WIN_SLOT + row * 16 + 8 * (h ^ ((row >> 3) & 1));
-}
-
 // one global_load_lds_dwordx4: lane L's 16 bytes land at LDS byte address lds + 16 L.  Inline asm: a
 // compiler-emitted LDS-DMA makes hipcc wait for it before every later LDS read it cannot tell apart
 // from the DMA's destination.  The kernel retires these itself (s_waitcnt vmcnt before the barrier
@@ -71,65 +69,6 @@ __device__ __forceinline__ void win_glds(const void* base, unsigned voff, unsign
                  : "=&s"(keep)
                  : "v"(voff), "s"(base), "s"(lds)
                  : "memory");
-}
-
-// IN statistics of the tile (as conv.hip rows_in_stats, BM 256 x BN 128): per column the tile's
-// count / mean / M2 / max / first argmax, merged over the four pixel waves in a fixed order
-__device__ __forceinline__ void win_stats(const floatx16 (&acc)[2][2], int p0, int n0, int Co, int wm, int wn,
-                                          int lane, int tid, float* lds, Part* __restrict__ parts, long long chunk) {
-    Part* sp = reinterpret_cast<Part*>(lds);  // [4][128]
-    const int hi = lane >> 5;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int colL = wn * 64 + j * 32 + (lane & 31);
-        float s = 0.f, mx = -INFINITY;
-        int am = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r)  // increasing pixel order (first maximum)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float v = acc[i][j][r];
-                s += v;
-                if (v > mx) { mx = v; am = p0 + win_pix(wm, i, r, hi); }
-            }
-        const float mean = s * (1.f / 32.f);
-        float m2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float dv = acc[i][j][r] - mean;
-                m2 = fmaf(dv, dv, m2);
-            }
-        const float mb = __shfl_xor(mean, 32, 64), m2b = __shfl_xor(m2, 32, 64), mxb = __shfl_xor(mx, 32, 64);
-        const int amb = __shfl_xor(am, 32, 64);
-        if (hi == 0) {
-            const float dl = mb - mean;
-            Part p;
-            p.cnt = 64.f;
-            p.mean = mean + 0.5f * dl;
-            p.m2 = m2 + m2b + dl * dl * 16.f;
-            p.mx = mx;
-            p.amax = am;
-            if (mxb > mx || (mxb == mx && amb < am)) { p.mx = mxb; p.amax = amb; }
-            p.pad[0] = p.pad[1] = p.pad[2] = 0;
-            sp[wm * WIN_BN + colL] = p;
-        }
-    }
-    __syncthreads();
-    if (tid < WIN_BN && n0 + tid < Co) {
-        Part a = sp[tid];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const Part b = sp[w * WIN_BN + tid];
-            const float tot = a.cnt + b.cnt, dl = b.mean - a.mean;
-            a.mean += dl * (b.cnt / tot);
-            a.m2 += b.m2 + dl * dl * (a.cnt * b.cnt / tot);
-            a.cnt = tot;
-            if (b.mx > a.mx || (b.mx == a.mx && b.amax < a.amax)) { a.mx = b.mx; a.amax = b.amax; }
-        }
-        parts[chunk * Co + n0 + tid] = a;
-    }
 }
 
 // The InstanceNorm backward's partial sums over a data-gradient tile (IBW instances): the output is
@@ -144,466 +83,6 @@ struct IbwArgs {
     int act, nchunk;
 };
 
-// y of the tile's outputs, every load issued before the first use
-__device__ __forceinline__ void win_ibw_load(float (&yv)[2][2][16], const IbwArgs& ib, long long obase, int p0, int Co,
-                                             int n0, int wm, int wn, int lane) {
-    const int kh = lane >> 5, l32 = lane & 31;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int pix = p0 + win_pix(wm, i, r, kh);
-                yv[i][j][r] = ib.y[obase + (long long)pix * Co + n0 + wn * 64 + j * 32 + l32];
-            }
-}
-
-__device__ __forceinline__ void win_ibw(const floatx16 (&acc)[2][2], const float (&yv)[2][2][16], const IbwArgs& ib,
-                                        int n, int p0, int H, int W, int Co, int n0, int wm, int wn, int lane, int tid,
-                                        int tile, float* lds) {
-    const int kh = lane >> 5, l32 = lane & 31;
-    Sum2* sp = reinterpret_cast<Sum2*>(lds);  // [4][128]; the k-loop's last barrier freed the LDS
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wn * 64 + j * 32 + l32;
-        const float s = ib.sc[(long long)n * Co + col], b = ib.sh[(long long)n * Co + col];
-        float sa = 0.f, sb = 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int pix = p0 + win_pix(wm, i, r, kh);
-                const int py = pix >> __builtin_ctz(W), px = pix & (W - 1);  // (W is a power of two)
-                if (py == 1 || py == H - 2 || px == 1 || px == W - 2) continue;  // the ring fold's pixels
-                const float xh = fmaf(yv[i][j][r], s, b);
-                const float g = acc[i][j][r] * act_grad(xh, ib.act);
-                sa += g;
-                sb = fmaf(g, xh, sb);
-            }
-        sa += __shfl_xor(sa, 32, 64);  // the same operand pair on both lanes: order-free
-        sb += __shfl_xor(sb, 32, 64);
-        if (kh == 0) sp[wm * 128 + wn * 64 + j * 32 + l32] = Sum2{sa, sb};
-    }
-    __syncthreads();
-    if (tid < 128 && n0 + tid < Co) {
-        Sum2 t = sp[tid];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            t.a += sp[w * 128 + tid].a;
-            t.b += sp[w * 128 + tid].b;
-        }
-        ib.parts[((long long)n * ib.nchunk + tile) * Co + n0 + tid] = t;
-    }
-}
-
-// NP: products per fragment pair (3: f16x3, hi*lo + lo*hi + hi*hi; 1: f16, hi*hi with the hi planes only);
-// IBW: the InstanceNorm-backward partial sums of the output (data gradients without addend)
-//
-// Schedule of a k-tile (one barrier each), built so that the fragment reads run ahead of the MFMAs
-// that consume them within the 256-register budget of two waves per SIMD (128 of them the two-level
-// accumulators):
-//   * B by LDS-DMA (win_glds): tile tt + 1 is issued into the other buffer at the top of tile tt and
-//     retired (vmcnt) before tile tt's barrier, so no register holds B in flight;
-//   * the window of the next slice one staging unit per k-tile (units 0, 1 in kernel rows 0, 1): only
-//     one unit's eight floats are live at a time.  Only the window's interior columns are loaded (two
-//     units per thread); the halo columns are written by the units of source columns 1 and W - 2
-//     (reflection) or zeroed once (zero padding);
-//   * B fragments one tap ahead (tap tx + 1's read before tap tx's MFMAs, pinned by sched_barrier);
-//   * waves 4-7 (the partners of waves 0-3 on their SIMDs) store their staging unit at the top of the
-//     next k-tile instead of after their MFMAs, so the two waves of a SIMD are not in the same phase.
-template <int NP, bool IBW>
-__global__ __launch_bounds__(WIN_NT, 1) void conv3_win_h3_kernel(WinArgs a, const float* __restrict__ src,
-                                                                 const _Float16* __restrict__ wh,
-                                                                 const _Float16* __restrict__ wl,
-                                                                 const float* __restrict__ rng,
-                                                                 const int* __restrict__ wexp,
-                                                                 const float* __restrict__ addend,
-                                                                 float* __restrict__ out, Part* __restrict__ parts,
-                                                                 IbwArgs ib) {
-    // f16x3: B k-tiles [2][6 = plane x tx][WIN_SLOT]; f16 (NP 1): B slices [2][9 taps][WIN_SLOT] (one
-    // barrier per slice, see below)
-    constexpr int BHALVES = NP == 3 ? 2 * 6 * WIN_SLOT : 2 * 9 * WIN_SLOT;
-    __shared__ __attribute__((aligned(16))) _Float16 smem[2 * 2 * WIN_PIX * 16 + BHALVES + 8];
-    _Float16* const Wn = smem;                               // [2][2][WIN_PIX][16]
-    _Float16* const Bs = smem + 2 * 2 * WIN_PIX * 16;
-    _Float16* const Wspare = Bs + BHALVES;                   // 16 bytes nobody reads
-
-    const int T = gridDim.x;
-    const int L = xcd_remap(blockIdx.x, T);
-    const int ntile = L % a.gy, mt = L / a.gy;
-    const int n = mt / a.tiles, tile = mt - n * a.tiles;
-    const int n0 = ntile * WIN_BN;
-    const int y0 = tile * a.R;                 // first image row of the tile
-    const int W = a.W, WP = a.W + 2, C = a.C;
-    const int K = 9 * C;                       // packed K (slice-major: (c/16)*144 + tap*16 + c%16)
-    const int nslice = C / 16;
-
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int l32 = lane & 31, kh = lane >> 5;
-
-    // the source exponent (ea, asc) is read in the prologue, its loads beside the first staging loads
-    int ea = 0;
-    float asc = 1.f;
-    const int eb = __builtin_amdgcn_readfirstlane(wexp[0]);
-
-    // window staging units of this thread: (pixel, 8-channel half) of the window's interior columns
-    // ((R + 2) x W pixels: 2 units per thread at W <= 128).  uoff: byte offset of the unit's source
-    // channel 0 (-1: zero padding); uwd: its window pixel (bits 0-15) and the halo pixel it also writes
-    // (bits 16-31), each + 1 (0: none)
-    const int nint = (a.R + 2) * W;
-    int uoff[WIN_UNITS], uwd[WIN_UNITS];
-#pragma unroll
-    for (int q = 0; q < WIN_UNITS; ++q) {
-        const int u = tid + q * WIN_NT;
-        const int ip = u >> 1, h = u & 1;
-        uoff[q] = -1;
-        uwd[q] = 0;
-        if (ip < nint) {
-            const int wr = ip >> __builtin_ctz(W), sx = ip & (W - 1);  // (W is a power of two)
-            int dup = -1;
-            int sy = y0 - 1 + wr;
-            bool ok = true;
-            if (a.reflect) {
-                sy = sy < 0 ? -sy : (sy >= a.H ? 2 * a.H - 2 - sy : sy);
-                if (sx == 1) dup = wr * WP;                   // column -1 reflects column 1
-                else if (sx == W - 2) dup = wr * WP + W + 1;  // column W reflects column W - 2
-            } else {
-                ok = sy >= 0 && sy < a.H;
-            }
-            uwd[q] = (wr * WP + sx + 2) | ((dup + 1) << 16);
-            if (ok) uoff[q] = (((n * a.H + sy) * W + sx) * C + 8 * h) * 4;
-        }
-    }
-    if (!a.reflect) {  // zero halo columns of both buffers and planes
-        for (int i = tid; i < 2 * 2 * (a.R + 2) * 2 * 2; i += WIN_NT) {
-            const int h = i & 1, side = (i >> 1) & 1, rest = i >> 2;
-            const int wr = rest % (a.R + 2), bp = rest / (a.R + 2);
-            *reinterpret_cast<f16x8*>(Wn + win_off(bp >> 1, bp & 1, wr * WP + side * (W + 1), h)) = f16x8{};
-        }
-    }
-    const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), (short)0, 0x7fffff00, 0x00020000);
-    float4 wq_[2];  // the unit in flight
-    auto win_load_u = [&](int q, int s) {  // unconditional (clamped offset): see the k loop
-        const int off = uoff[q] >= 0 ? uoff[q] + s * 64 : 0x7fffffbf;  // 16 channels = 64 B per slice
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(srsrc, off, 0, 0);
-        u32x4 v1 = __builtin_amdgcn_raw_buffer_load_b128(srsrc, off + 16, 0, 0);
-        __builtin_memcpy(&wq_[0], &v0, 16);
-        __builtin_memcpy(&wq_[1], &v1, 16);
-    };
-    // unconditional store (a unit past the window writes the spare slot): a store under a branch lets
-    // the compiler sink the unit's load into the branch, next to its use
-    auto win_store_u = [&](int q, int buf) {
-        const int h = (tid + q * WIN_NT) & 1;
-        const int wp = (uwd[q] & 0xffff) - 1, wd = (uwd[q] >> 16) - 1;
-        f16x8 hi, lo;
-        split8h(wq_[0], wq_[1], asc, hi, lo);
-        *reinterpret_cast<f16x8*>(wp >= 0 ? Wn + win_off(buf, 0, wp, h) : Wspare) = hi;
-        if constexpr (NP == 3) *reinterpret_cast<f16x8*>(wp >= 0 ? Wn + win_off(buf, 1, wp, h) : Wspare) = lo;
-        if (wd >= 0) {
-            *reinterpret_cast<f16x8*>(Wn + win_off(buf, 0, wd, h)) = hi;
-            if constexpr (NP == 3) *reinterpret_cast<f16x8*>(Wn + win_off(buf, 1, wd, h)) = lo;
-        }
-    };
-
-    // B k-tile (slice s, kernel row ty) by LDS-DMA: 2 planes x 3 tx slots x 128 rows = 24 blocks of
-    // 1 KB (plane, tx slot, 32-row block), three per wave; a block's LDS image is lane-linear (lane L ->
-    // row L / 2, half position L % 2), so the wb_off swizzle goes on the source side: lane L fetches
-    // half (L % 2) ^ bit 3 of its row.  The lane part of the source offset is the same for the three
-    // blocks (bit 3 of the row is bit 3 of L / 2); the block part and the plane are wave-uniform.
-    unsigned dsu[3], ddst[3];
-    const _Float16* dbase[3];
-    const unsigned dlane = 2u * (unsigned)((n0 + (lane >> 1)) * K + 8 * ((lane & 1) ^ ((lane >> 4) & 1)));
-    {
-        const unsigned bs_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) _Float16*)Bs;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int c = __builtin_amdgcn_readfirstlane(wid) * 3 + i, pl = c / 12, rem = c - pl * 12;
-            const int tx = rem >> 2, rb = rem & 3;
-            dsu[i] = 2u * (unsigned)(rb * 32 * K + tx * 16);
-            dbase[i] = pl ? wl : wh;
-            ddst[i] = __builtin_amdgcn_readfirstlane(bs_lds + 2u * (unsigned)((pl * 3 + tx) * WIN_SLOT + rb * 32 * 16));
-        }
-    }
-    auto b_dma = [&](int t, int buf) {  // B tile t into buffer buf
-        const int s_ = t / 3, ty_ = t - 3 * (t / 3);
-        const unsigned kb = 2u * (unsigned)(s_ * 144 + ty_ * 48);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) win_glds(dbase[i], dlane + (dsu[i] + kb), ddst[i] + 2u * (unsigned)(buf * 6 * WIN_SLOT));
-    };
-
-    // window pixel of this lane's block-0 output pixel 2m (tap (0, 0) = the window's top-left); its
-    // block-1 pixel 2m + 1 is the next one (W is even: the pair shares a row)
-    int wbe;
-    {
-        const int q = wm * 64 + 2 * l32;
-        wbe = (q >> __builtin_ctz(W)) * WP + (q & (W - 1));
-    }
-
-    floatx16 acc[2][2], t[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; t[i][j][r] = 0.f; }
-
-    if constexpr (NP == 1) {
-        // f16: one product per fragment pair, so a 48-k tile holds only 12 MFMAs per wave; instead the
-        // whole slice (9 taps, hi planes only) is staged per barrier: 36 MFMAs per wave between
-        // barriers.  One accumulation level: the fp32 chain over all 9 C products (K <= 4608) rounds far
-        // below the fp16 operands' 2^-11, so the two-level sum of the f16x3 path buys nothing here.  B slice by LDS-DMA, 36 blocks of 1 KB (tap, 32-row block), blocks w, w + 8, ...
-        // of wave w.
-        unsigned sdst[5], ssu[5];
-        {
-            const unsigned bs_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) _Float16*)Bs;
-            const int w = __builtin_amdgcn_readfirstlane(wid);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                const int c = w + 8 * i < 36 ? w + 8 * i : 35, tap = c >> 2, rb = c & 3;
-                ssu[i] = 2u * (unsigned)(rb * 32 * K + tap * 16);
-                sdst[i] = __builtin_amdgcn_readfirstlane(bs_lds + 2u * (unsigned)(tap * WIN_SLOT + rb * 32 * 16));
-            }
-        }
-        const bool fifth = wid + 32 < 36;  // wave-uniform: waves 0-3 issue a fifth block
-        auto s_dma = [&](int sl, int buf) {
-            const unsigned kb = 2u * (unsigned)(sl * 144);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) win_glds(wh, dlane + (ssu[i] + kb), sdst[i] + 2u * (unsigned)(buf * 9 * WIN_SLOT));
-            if (fifth) win_glds(wh, dlane + (ssu[4] + kb), sdst[4] + 2u * (unsigned)(buf * 9 * WIN_SLOT));
-        };
-        // prologue: every load of slice 0 (and the exponent's) in flight before the first store
-        s_dma(0, 0);
-        win_load_u(1, 0);
-        const float4 wp1[2] = {wq_[0], wq_[1]};
-        win_load_u(0, 0);
-        ea = f16x3_exp(rng, a.rng_n);
-        asc = __builtin_ldexpf(1.f, ea);
-        win_store_u(0, 0);
-        wq_[0] = wp1[0];
-        wq_[1] = wp1[1];
-        win_store_u(1, 0);
-        __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): the DMA has landed
-        __syncthreads();
-        auto sloop = [&](auto role_tag) {
-            constexpr int ROLE = decltype(role_tag)::value;
-            for (int s = 0; s < nslice; ++s) {
-                const int buf = s & 1;
-                const int sn = s + 1 < nslice ? s + 1 : s;
-                // the next slice into the other buffers (last read before this slice's top barrier):
-                // B by DMA now, the window's two units loaded now and stored after the kernel row that
-                // is this wave's staging point (ROLE 0: the last, ROLE 1: the second)
-                s_dma(sn, buf ^ 1);
-                win_load_u(1, sn);  // unit 1 into wq_, moved to wq1
-                const float4 wq1[2] = {wq_[0], wq_[1]};
-                win_load_u(0, sn);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ty = 0; ty < 3; ++ty) {
-                    f16x8 fh[4];
-#pragma unroll
-                    for (int f = 0; f < 4; ++f)
-                        fh[f] = *reinterpret_cast<const f16x8*>(Wn + win_off(buf, 0, wbe + ty * WP + f, kh));
-                    f16x8 pb[2][2];
-                    auto rd_b = [&](int tx, int slot) {
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const int row = wn * 64 + j * 32 + l32;
-                            pb[slot][j] = *reinterpret_cast<const f16x8*>(
-                                Bs + (buf * 9 + ty * 3 + tx) * WIN_SLOT + row * 16 + 8 * (kh ^ ((row >> 3) & 1)));
-                        }
-                    };
-                    rd_b(0, 0);
-#pragma unroll
-                    for (int tx = 0; tx < 3; ++tx) {
-                        if (tx < 2) rd_b(tx + 1, (tx + 1) & 1);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j)
-                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[tx + i], pb[tx & 1][j], acc[i][j], 0, 0, 0);
-                    }
-                    if (ty == (ROLE == 0 ? 2 : 1)) {  // staging point of this wave (kernel row 2 / 1)
-                        __builtin_amdgcn_sched_barrier(0);
-                        win_store_u(0, buf ^ 1);
-                        wq_[0] = wq1[0];
-                        wq_[1] = wq1[1];
-                        win_store_u(1, buf ^ 1);
-                    }
-                }
-                __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): this wave's DMAs landed
-                __syncthreads();
-            }
-        };
-        if (wid >= 4) sloop(std::integral_constant<int, 1>{});
-        else sloop(std::integral_constant<int, 0>{});
-    } else {
-    // prologue: window of slice 0, B tile 0, every load (and the exponent's) in flight before the first
-    // store
-    b_dma(0, 0);
-    win_load_u(1, 0);
-    const float4 wp1[2] = {wq_[0], wq_[1]};
-    win_load_u(0, 0);
-    ea = f16x3_exp(rng, a.rng_n);
-    asc = __builtin_ldexpf(1.f, ea);
-    win_store_u(0, 0);
-    wq_[0] = wp1[0];
-    wq_[1] = wp1[1];
-    win_store_u(1, 0);
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): the DMA has landed
-    __syncthreads();
-
-    // every global load below is unconditional (offsets clamped at the end): a load under a branch
-    // makes the compiler wait for all outstanding loads (vmcnt(0)) at the next consumer
-    const int last = 3 * nslice - 1;
-    auto kloop = [&](auto role_tag) {
-        constexpr int ROLE = decltype(role_tag)::value;
-        for (int s = 0; s < nslice; ++s) {
-            const int wbuf = s & 1;
-            const int sn = s + 1 < nslice ? s + 1 : s;
-#pragma unroll
-            for (int ty = 0; ty < 3; ++ty) {
-                const int tt = 3 * s + ty, bbuf = tt & 1;
-                // staging of the next slice's window (buffer wbuf ^ 1: last read before the previous
-                // slice's last barrier): unit ty loaded here, stored after this k-tile's MFMAs (ROLE 0)
-                // or at the top of the next k-tile (ROLE 1)
-                if constexpr (ROLE == 1) {
-                    if (ty >= 1) win_store_u(ty - 1, wbuf ^ 1);
-                }
-                if (ty < WIN_UNITS) win_load_u(ty, sn);
-                // B tile tt + 1 into the other buffer (last read before the previous barrier); past the
-                // end a repeat nobody reads
-                b_dma(tt + 1 < last ? tt + 1 : last, bbuf ^ 1);
-                __builtin_amdgcn_sched_barrier(0);  // the loads stay at the top of the k-tile
-                // A fragments of window pixels wbe + ty * WP + 0 .. 3: block i at tap tx takes fragment tx + i
-                f16x8 fh[4], fl[4];
-#pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    const int wpix = wbe + ty * WP + f;
-                    fh[f] = *reinterpret_cast<const f16x8*>(Wn + win_off(wbuf, 0, wpix, kh));
-                    if constexpr (NP == 3) fl[f] = *reinterpret_cast<const f16x8*>(Wn + win_off(wbuf, 1, wpix, kh));
-                }
-                // B fragments one tap ahead: tap tx + 1's are read before tap tx's MFMAs
-                f16x8 pbh[2][2], pbl[2][2];
-                auto rd_b = [&](int tx, int slot) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int row = wn * 64 + j * 32 + l32;
-                        pbh[slot][j] = *reinterpret_cast<const f16x8*>(Bs + wb_off(bbuf, 0, tx, row, kh));
-                        if constexpr (NP == 3) pbl[slot][j] = *reinterpret_cast<const f16x8*>(Bs + wb_off(bbuf, 1, tx, row, kh));
-                    }
-                };
-                rd_b(0, 0);
-#pragma unroll
-                for (int tx = 0; tx < 3; ++tx) {
-                    if (tx < 2) rd_b(tx + 1, (tx + 1) & 1);
-                    __builtin_amdgcn_sched_barrier(0);  // the reads stay ahead of this tap's MFMAs
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const f16x8 bh = pbh[tx & 1][j];
-                            if constexpr (NP == 3) {
-                                t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fl[tx + i], bh, t[i][j], 0, 0, 0);
-                                t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[tx + i], pbl[tx & 1][j], t[i][j], 0, 0, 0);
-                            }
-                            t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[tx + i], bh, t[i][j], 0, 0, 0);
-                        }
-                }
-                if constexpr (ROLE == 0) {
-                    // (below the MFMAs: hoisted into them, the split would wait for the unit's load there)
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (ty < WIN_UNITS) win_store_u(ty, wbuf ^ 1);
-                }
-                __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): this wave's DMAs (and window loads) landed
-                __syncthreads();
-            }
-            // close the slice's accumulation chain (144 k)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc[i][j] += t[i][j];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) t[i][j][r] = 0.f;
-                }
-        }
-    };
-    if (wid >= 4) kloop(std::integral_constant<int, 1>{});  // (wave-uniform branch)
-    else kloop(std::integral_constant<int, 0>{});
-    }
-
-    // epilogue: undo the operand scales, + addend, NHWC store, IN statistics
-    const int eab = -(ea + eb);
-    const int p0 = y0 * W;  // the tile's first pixel within the image
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], eab);
-    const long long obase = (long long)n * a.H * W * a.Co;
-    auto ooff = [&](int i, int j, int r) {
-        const int pix = p0 + win_pix(wm, i, r, kh);
-        return obase + (long long)pix * a.Co + n0 + wn * 64 + j * 32 + l32;
-    };
-
-    if (addend) {  // wave-uniform: all 64 addend loads issued before the first use
-        floatx16 ad[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ad[i][j][r] = addend[ooff(i, j, r)];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) out[ooff(i, j, r)] = acc[i][j][r] + ad[i][j][r];
-    } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) out[ooff(i, j, r)] = acc[i][j][r];
-    }
-    if (parts) win_stats(acc, p0, n0, a.Co, wm, wn, lane, tid, reinterpret_cast<float*>(smem), parts,
-                         (long long)n * a.tiles + tile);
-    if constexpr (IBW) {  // (y loaded here, after the stores: issuing them earlier spills ~70 VGPRs)
-        float yv[2][2][16];
-        win_ibw_load(yv, ib, obase, p0, a.Co, n0, wm, wn, lane);
-        win_ibw(acc, yv, ib, n, p0, a.H, W, a.Co, n0, wm, wn, lane, tid, tile, reinterpret_cast<float*>(smem));
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// The f16x3 window conv on v_mfma_f32_16x16x32_f16 (conv3_win16_kernel: same tile, operands, window
-// and B staging as conv3_win_h3_kernel above).  Both MFMA shapes do the same MACs per fragment byte,
-// but under the package power limit the 16x16x32 form sustains ~12 % more FLOP/s: 1758 against 1562
-// TFLOP/s of f16x3 products in a bare LDS-read + MFMA loop with every CU busy on random operands
-// (scripts/probes/mfma_shape_power.hip, profiles/r06b/; MI355X_MICROARCH.md, DVFS item 7).
-//
-// K = 32 per MFMA = two (slice, tap) units of 16 channels: the fragments' k groups 0, 1 (lanes 0-31)
-// take unit 2j, k groups 2, 3 (lanes 32-63) unit 2j + 1 -- the packed B's k = 16 unit + channel, so a
-// k-step is 32 consecutive packed k.  A slice has nine taps: the k-steps walk the 18 units of a PAIR
-// of slices, 9 k-steps, k-step 4 taking tap 8 of the even slice and tap 0 of the odd one.  The even
-// slice of a pair sits in window buffer 0, the odd one in buffer 1; the next odd slice is staged
-// during k-steps 0-3 (buffer 1 is free after the previous pair's k-step 8), the next even slice
-// during k-steps 5-8 (buffer 0 is free after k-step 4), one unit in flight per thread as above.
-// One barrier per k-step: B (128 output-channel rows x 32 k x 2 planes, 16 KB) by LDS-DMA into the
-// other of two buffers.  Per k-step and wave: 4 x 4 blocks of 16 x 16 x 3 products = 48 MFMAs.
-// Row block i of wave wm holds the 16 consecutive tile pixels wm * 64 + 16 i + (lane & 15) (W >= 16:
-// a block never crosses an image row), so the window needs no swizzle: the 16 lanes of a
-// ds_read_b128 lane group read 16 distinct 16-byte bank groups (pixel stride 32 B, the two channel
-// halves on odd / even groups).  A B row (output channel co) holds its four 8-k groups rotated by
-// 2 * ((co >> 2) & 3), which makes the B reads conflict-free too.  Two-level accumulation: chains of
-// 5 and 4 k-steps (160 / 128 k), added to the running sum.
 constexpr int W16_BSLOT = 128 * 32;  // halves per B plane and k-step
 
 __device__ __forceinline__ int w16_off(int buf, int pl, int wpix, int h) {
@@ -612,7 +91,8 @@ __device__ __forceinline__ int w16_off(int buf, int pl, int wpix, int h) {
 
 // IN statistics of the tile from the 16x16 accumulator layout (lane: column lane & 15 of each block,
 // rows 4 (lane >> 4) + r): per column over the lane's 16 pixels, merged with lanes ^ 16 and ^ 32, then
-// over the four pixel waves in a fixed order (as win_stats)
+// over the four pixel waves in a fixed order (the tile's count / mean / M2 / max / first argmax per
+// column, as conv.hip rows_in_stats with BM 256 x BN 128)
 __device__ __forceinline__ void win16_stats(const f32x4v (&acc)[4][4], int p0, int n0, int Co, int wm, int wn,
                                             int lane, int tid, float* lds, Part* __restrict__ parts, long long chunk) {
     Part* sp = reinterpret_cast<Part*>(lds);  // [4][128]
@@ -674,7 +154,7 @@ __device__ __forceinline__ void win16_stats(const f32x4v (&acc)[4][4], int p0, i
     }
 }
 
-// win_ibw for the 16x16 accumulator layout
+// the IbwArgs partial sums of the tile from the 16x16 accumulator layout (yv: y at the tile's outputs)
 __device__ __forceinline__ void win16_ibw(const f32x4v (&acc)[4][4], const float (&yv)[4][4][4], const IbwArgs& ib,
                                           int n, int p0, int H, int W, int Co, int n0, int wm, int wn, int lane,
                                           int tid, int tile, float* lds) {
@@ -754,7 +234,10 @@ __global__ __launch_bounds__(WIN_NT, 1) void conv3_win16_kernel(WinArgs a, const
     float asc = 1.f;
     const int eb = __builtin_amdgcn_readfirstlane(wexp[0]);
 
-    // window staging units (as conv3_win_h3_kernel)
+    // window staging units of this thread: (pixel, 8-channel half) of the window's interior columns
+    // ((R + 2) x W pixels: 2 units per thread at W <= 128).  uoff: byte offset of the unit's source
+    // channel 0 (-1: zero padding); uwd: its window pixel (bits 0-15) and the halo pixel it also writes
+    // (bits 16-31), each + 1 (0: none)
     const int nint = (a.R + 2) * W;
     int uoff[WIN_UNITS], uwd[WIN_UNITS];
 #pragma unroll
@@ -787,9 +270,12 @@ __global__ __launch_bounds__(WIN_NT, 1) void conv3_win16_kernel(WinArgs a, const
         }
     }
     const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), (short)0, 0x7fffff00, 0x00020000);
-    f32x4v wq_[2];  // (ext vectors: tied operands of the wait below)
+    f32x4v wq_[2];  // the unit in flight (ext vectors: tied operands of the wait below)
+    // every global load is unconditional (a unit outside the source reads at a clamped offset, zeros):
+    // a load under a branch makes the compiler wait for all outstanding loads (vmcnt(0)) at the next
+    // consumer
     auto win_load_into = [&](int q, int s, f32x4v (&dst)[2]) {
-        const int off = uoff[q] >= 0 ? uoff[q] + s * 64 : 0x7fffffbf;
+        const int off = uoff[q] >= 0 ? uoff[q] + s * 64 : 0x7fffffbf;  // 16 channels = 64 B per slice
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(srsrc, off, 0, 0);
         u32x4 v1 = __builtin_amdgcn_raw_buffer_load_b128(srsrc, off + 16, 0, 0);
@@ -797,6 +283,8 @@ __global__ __launch_bounds__(WIN_NT, 1) void conv3_win16_kernel(WinArgs a, const
         __builtin_memcpy(&dst[1], &v1, 16);
     };
     auto win_load_u = [&](int q, int s) { win_load_into(q, s, wq_); };
+    // unconditional store (a unit past the window writes the spare slot): a store under a branch lets
+    // the compiler sink the unit's load into the branch, next to its use
     auto win_store_u = [&](int q, int buf) {
         const int h = (tid + q * WIN_NT) & 1;
         const int wp = (uwd[q] & 0xffff) - 1, wd = (uwd[q] >> 16) - 1;
@@ -2056,9 +1544,17 @@ int wgrad_win_launch(const dcs_conv_desc& d, const float* dy, const float* x, fl
 
 namespace {
 
+// the padded-grid ring on ring16_kernel (d: the data gradient's descriptor): RG_COPIES ring copies (one
+// per tap)
+bool ring16_ok(const dcs_conv_desc& d) {
+    return d.Cs == 256 && d.Co % 256 == 0 && d.Hs >= 2 && d.Ws >= 2;
+}
+
+// the one place that decides whether the window kernels take a descriptor (dcs_conv3_win_ok): forward,
+// conv3_win16_kernel; data gradient, conv3_win16_kernel for the interior and ring16_kernel for the ring
 int win_check(const dcs_conv_desc& d, bool fwd) {
-    const bool geom = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.up == 1 && !d.parity && d.Cs % 16 == 0 &&
-                      d.Co % WIN_BN == 0 && d.Ws >= 2 && d.Ws <= 128 && 256 % d.Ws == 0 && d.Hs % (256 / d.Ws) == 0 &&
+    const bool geom = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.up == 1 && !d.parity && d.Cs % 32 == 0 &&
+                      d.Co % WIN_BN == 0 && d.Ws >= 16 && d.Ws <= 128 && 256 % d.Ws == 0 && d.Hs % (256 / d.Ws) == 0 &&
                       d.s_c == 1 && d.s_w == d.Cs && d.s_h == (long long)d.Ws * d.Cs &&
                       d.s_n == (long long)d.Hs * d.Ws * d.Cs && d.csplit == d.Cs &&
                       d.epi_act == DCS_ACT_NONE && (d.mma == DCS_MMA_F16X3 || d.mma == DCS_MMA_F16) && d.rng_a && d.rng_a_n > 0 &&
@@ -2066,7 +1562,8 @@ int win_check(const dcs_conv_desc& d, bool fwd) {
                       d.pro_act == DCS_ACT_NONE;
     if (!geom) return 0;
     if (fwd) return d.Ho == d.Hs && d.Wo == d.Ws && d.pt == 1 && d.pl == 1;
-    return d.Ho == d.Hs + 2 && d.Wo == d.Ws + 2 && d.pt == 2 && d.pl == 2 && d.pad_mode == DCS_PAD_ZERO;
+    return d.Ho == d.Hs + 2 && d.Wo == d.Ws + 2 && d.pt == 2 && d.pl == 2 && d.pad_mode == DCS_PAD_ZERO &&
+           ring16_ok(d);
 }
 
 int launch_win(const dcs_conv_desc& d, int H, int W, int reflect, const float* src, const void* wh, const void* wl,
@@ -2077,9 +1574,8 @@ int launch_win(const dcs_conv_desc& d, int H, int W, int reflect, const float* s
     a.R = 256 / W; a.tiles = H / a.R; a.gy = d.Co / WIN_BN; a.rng_n = d.rng_a_n;
     const unsigned blocks = (unsigned)(a.N * a.tiles * a.gy);
     const IbwArgs ib = ibw ? *ibw : IbwArgs{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (W >= 16 && d.Cs % 32 == 0) {  // the 16x16x32 kernel
-        const _Float16* h = reinterpret_cast<const _Float16*>(wh);
-        const _Float16* l = reinterpret_cast<const _Float16*>(wl);
+    const _Float16* h = reinterpret_cast<const _Float16*>(wh);
+    const _Float16* l = reinterpret_cast<const _Float16*>(wl);
 #define DCS_WIN16_LAUNCH(IBW_, WIDE_)                                                                              \
     if (d.mma == DCS_MMA_F16X3)                                                                                \
         hipLaunchKernelGGL((conv3_win16_kernel<3, IBW_, WIDE_>), dim3(blocks), dim3(WIN_NT), 0, s, a, src, h, l,   \
@@ -2087,32 +1583,15 @@ int launch_win(const dcs_conv_desc& d, int H, int W, int reflect, const float* s
     else                                                                                                        \
         hipLaunchKernelGGL((conv3_win16_kernel<1, IBW_, WIDE_>), dim3(blocks), dim3(WIN_NT), 0, s, a, src, h, l,   \
                            d.rng_a, wexp, addend, out, parts, ib);
-        if (W >= 64) {
-            if (ibw) { DCS_WIN16_LAUNCH(true, true) } else { DCS_WIN16_LAUNCH(false, true) }
-        } else {
-            if (ibw) { DCS_WIN16_LAUNCH(true, false) } else { DCS_WIN16_LAUNCH(false, false) }
-        }
-#undef DCS_WIN16_LAUNCH
-        return check_launch("conv3_win16");
-    }
-#define DCS_WIN_LAUNCH(NP_, IBW_)                                                                                 \
-    hipLaunchKernelGGL((conv3_win_h3_kernel<NP_, IBW_>), dim3(blocks), dim3(WIN_NT), 0, s, a, src,                     \
-                       reinterpret_cast<const _Float16*>(wh), reinterpret_cast<const _Float16*>(wl), d.rng_a, wexp, addend, \
-                       out, parts, ib);
-    if (d.mma == DCS_MMA_F16) {
-        if (ibw) { DCS_WIN_LAUNCH(1, true) } else { DCS_WIN_LAUNCH(1, false) }
+    if (W >= 64) {
+        if (ibw) { DCS_WIN16_LAUNCH(true, true) } else { DCS_WIN16_LAUNCH(false, true) }
     } else {
-        if (ibw) { DCS_WIN_LAUNCH(3, true) } else { DCS_WIN_LAUNCH(3, false) }
+        if (ibw) { DCS_WIN16_LAUNCH(true, false) } else { DCS_WIN16_LAUNCH(false, false) }
     }
-#undef DCS_WIN_LAUNCH
-    return check_launch("conv3_win");
+#undef DCS_WIN16_LAUNCH
+    return check_launch("conv3_win16");
 }
 
-// the padded-grid ring on ring16_kernel (d: the data gradient's descriptor, win_check'ed): RG_COPIES ring
-// copies (one per tap)
-bool ring16_ok(const dcs_conv_desc& d) {
-    return d.Cs == 256 && d.Co % 256 == 0 && d.Hs >= 2 && d.Ws >= 2;
-}
 int launch_ring16(const dcs_conv_desc& d, const float* dy, const void* wh, const void* wl, const int* wexp, float* ring,
                   hipStream_t s) {
     RingArgs a;
@@ -2131,14 +1610,11 @@ int launch_ring16(const dcs_conv_desc& d, const float* dy, const void* wh, const
 
 }  // namespace
 
-// conv.hip: the generic rows pass (ring rows of the padded data gradient) and the ring fold
-int conv_rows_impl(const dcs_conv_desc* dp, const float* src, const float* src2, const float* wpack, const float* bias,
-                   const float* psc, const float* psh, float* out, Part* parts, int* bm_used, void* stream, int fold);
+// conv.hip: the ring fold
 int reflect_ring_fold(const float* ring, float* dx, int N, int H, int W, int C, int nsplit, hipStream_t s);
 int reflect_ring_fold_ibw(const float* ring, float* dx, int N, int H, int W, int C, int nsplit, const float* y,
                           const float* sc, const float* sh, int act, Sum2* parts, int nchunk, int chunk0, int nfc,
                           hipStream_t s);
-int ring_ksplit(const dcs_conv_desc& d);
 constexpr int IBW_FOLD_CHUNKS = 64;  // partial-sum chunks of the ring fold per image (its blocks: 64 per image)
 
 }  // namespace dcs
@@ -2175,7 +1651,7 @@ extern "C" int dcs_conv3_win_in_stats(const dcs_conv_desc* dp, const float* src,
     const dcs_conv_desc& d = *dp;
     if (!win_check(d, true))
         return fail(DCS_E_INVALID, "conv3_win: needs a 3x3 stride-1 'same' f16x3 conv over contiguous NHWC rows "
-                                   "(W <= 128, 256 % W == 0, H % (256 / W) == 0, Cs % 16 == 0, Co % 128 == 0, "
+                                   "(16 <= W <= 128, 256 % W == 0, H % (256 / W) == 0, Cs % 32 == 0, Co % 128 == 0, "
                                    "no prologue)");
     const int tiles = d.Hs / (256 / d.Ws);
     if (parts) {
@@ -2190,7 +1666,8 @@ extern "C" int dcs_conv3_win_in_stats(const dcs_conv_desc* dp, const float* src,
 extern "C" int dcs_conv_dgrad_reflect_win(const dcs_conv_desc* dp, const float* dy, const float* wpack,
                                           const void* w_hi, const void* w_lo, const int* wexp, const float* addend,
                                           float* dx, float* ring, void* stream) {
-    if (!dp || !dy || !wpack || !w_hi || !w_lo || !wexp || !dx || !ring)
+    (void)wpack;  // unused by the window route
+    if (!dp || !dy || !w_hi || !w_lo || !wexp || !dx || !ring)
         return fail(DCS_E_INVALID, "conv_dgrad_reflect_win: null pointer");
     const dcs_conv_desc& d = *dp;
     if (!win_check(d, false) || d.Co % 4 != 0 || d.Hs < 4 || d.Ws < 4)
@@ -2200,13 +1677,9 @@ extern "C" int dcs_conv_dgrad_reflect_win(const dcs_conv_desc* dp, const float* 
     // interior: a 'same' zero-pad conv of dy over the flipped weights, straight into dx (+ addend)
     int e = launch_win(d, d.Hs, d.Ws, 0, dy, w_hi, w_lo, wexp, addend, dx, nullptr, s);
     if (e) return e;
-    // the padded grid's one-pixel ring (ring16_kernel, else the generic rows pass), folded onto the border
-    if (ring16_ok(d)) {
-        if ((e = launch_ring16(d, dy, w_hi, w_lo, wexp, ring, s))) return e;
-        return reflect_ring_fold(ring, dx, d.N, d.Ho - 2, d.Wo - 2, d.Co, RG_COPIES, s);
-    }
-    if ((e = conv_rows_impl(&d, dy, nullptr, wpack, nullptr, nullptr, nullptr, ring, nullptr, nullptr, stream, 2))) return e;
-    return reflect_ring_fold(ring, dx, d.N, d.Ho - 2, d.Wo - 2, d.Co, ring_ksplit(d), s);
+    // the padded grid's one-pixel ring (ring16_kernel), folded onto the border
+    if ((e = launch_ring16(d, dy, w_hi, w_lo, wexp, ring, s))) return e;
+    return reflect_ring_fold(ring, dx, d.N, d.Ho - 2, d.Wo - 2, d.Co, RG_COPIES, s);
 }
 
 extern "C" size_t dcs_conv_dgrad_reflect_win_inbwd_parts_size(const dcs_conv_desc* dp) {
@@ -2220,7 +1693,8 @@ extern "C" int dcs_conv_dgrad_reflect_win_inbwd(const dcs_conv_desc* dp, const f
                                                 const void* w_hi, const void* w_lo, const int* wexp, float* dx,
                                                 float* ring, const float* y, const float* scale, const float* shift,
                                                 int act, void* parts, size_t parts_bytes, int* nchunk, void* stream) {
-    if (!dp || !dy || !wpack || !w_hi || !w_lo || !wexp || !dx || !ring || !y || !scale || !shift || !parts || !nchunk)
+    (void)wpack;  // unused by the window route
+    if (!dp || !dy || !w_hi || !w_lo || !wexp || !dx || !ring || !y || !scale || !shift || !parts || !nchunk)
         return fail(DCS_E_INVALID, "conv_dgrad_reflect_win_inbwd: null pointer");
     const dcs_conv_desc& d = *dp;
     if (!win_check(d, false) || d.Co % 4 != 0 || 256 % (d.Co / 4) || d.Hs < 4 || d.Ws < 4)
@@ -2236,11 +1710,8 @@ extern "C" int dcs_conv_dgrad_reflect_win_inbwd(const dcs_conv_desc* dp, const f
     const IbwArgs ib{y, scale, shift, reinterpret_cast<Sum2*>(parts), act, nch};
     int e = launch_win(d, d.Hs, d.Ws, 0, dy, w_hi, w_lo, wexp, nullptr, dx, nullptr, s, &ib);
     if (e) return e;
-    const bool r16 = ring16_ok(d);
-    if (r16) e = launch_ring16(d, dy, w_hi, w_lo, wexp, ring, s);
-    else e = conv_rows_impl(&d, dy, nullptr, wpack, nullptr, nullptr, nullptr, ring, nullptr, nullptr, stream, 2);
-    if (e) return e;
+    if ((e = launch_ring16(d, dy, w_hi, w_lo, wexp, ring, s))) return e;
     *nchunk = nch;
-    return reflect_ring_fold_ibw(ring, dx, d.N, d.Hs, d.Ws, d.Co, r16 ? RG_COPIES : ring_ksplit(d), y, scale, shift, act,
+    return reflect_ring_fold_ibw(ring, dx, d.N, d.Hs, d.Ws, d.Co, RG_COPIES, y, scale, shift, act,
                                  reinterpret_cast<Sum2*>(parts), nch, tiles, IBW_FOLD_CHUNKS, s);
 }

@@ -473,9 +473,9 @@ class ConvGeom:
     @property
     def win(self) -> bool:
         """f16x3 window kernel for this geometry (3x3 stride-1 pad-1, csrc/conv_win.hip): the packs
-        also carry the pre-split fp16 planes (``_dcs_h3``); used where the call's image fits."""
+        also carry the pre-split fp16 planes (``_dcs_h3``); used where dcs_conv3_win_ok takes the call."""
         return (_WIN and _h3() and self.k == 3 and self.stride == 1 and self.up == 1
-                and self.pads == (1, 1, 1, 1) and self.cin % 16 == 0 and self.cout % 128 == 0)
+                and self.pads == (1, 1, 1, 1) and self.cin % 32 == 0 and self.cout % 128 == 0)
 
     def _attach_h3(self, wpack: torch.Tensor, w: torch.Tensor, flip: int) -> torch.Tensor:
         ncols = self.cin if flip else self.cout

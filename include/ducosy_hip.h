@@ -209,17 +209,18 @@ int dcs_range_parts(const float* x, int n_img, int64_t per_img, int C, const flo
  * dcs_conv3_win_ok(d, dgrad): 1 if d is a geometry these passes cover: dgrad = 0, the forward of a
  * 3x3 stride-1 pad-1 conv (d as for dcs_conv_rows_in_stats); dgrad = 1, the padded-grid data gradient
  * (d as for dcs_conv_dgrad_reflect); both with mma = DCS_MMA_F16X3 and rng_a set, contiguous NHWC,
- * W <= 128, 256 % W == 0, H % (256 / W) == 0, Cs % 16 == 0, Co % 128 == 0.
+ * 16 <= W <= 128, 256 % W == 0, H % (256 / W) == 0, Cs % 32 == 0, Co % 128 == 0; the data gradient
+ * also Cs == 256 and Co % 256 == 0 (its ring kernel).  It is the single place that decides: every
+ * other geometry takes the rows pass (dcs_conv_rows_in_stats / dcs_conv_dgrad_reflect).
  * dcs_conv3_win_in_stats: forward + IN statistics partials (as dcs_conv_rows_in_stats; parts = NULL
  * for none; *nchunk = H * W / 256).
  * dcs_conv_dgrad_reflect_win: the data gradient of a ReflectionPad2d(1) + 3x3 conv
  * (dcs_conv_dgrad_reflect's contract, plus the pre-split flipped weights): the interior by the
  * window pass (+ addend), the padded grid's one-pixel ring into ring (dcs_conv_dgrad_reflect_ring_size
  * bytes, any allocation) and folded onto dx's border; w_hi / w_lo: a flip = 1 pack with ncols == d->Co.
- * The ring: with Cs == 256 and Co % 256 == 0 one GEMM per ring segment and tap over the pack's tap-major
- * copy (csrc/conv_win.hip ring16_kernel: three ring
- * copies summed in tap order, independent of the batch), otherwise the rows pass over wpack (fp32
- * kind 1 | DCS_PACK_KSLICE with its range record). */
+ * The ring: one GEMM per ring segment and tap over the pack's tap-major copy (csrc/conv_win.hip
+ * ring16_kernel: three ring copies summed in tap order, independent of the batch).  wpack is unused by
+ * the window route (may be NULL); the parameter stays for the ABI. */
 size_t dcs_pack_weights_h3_scratch_size(void);
 int dcs_pack_weights_h3(const float* w, int Cout, int Cin, int flip, int ncols, void* out_hi, void* out_lo,
                         float* scratch, int* wexp, void* stream);

@@ -3,7 +3,9 @@ modules/model.py:72-80) against float64 references of the same fp32 operands:
   * forward (reflection pad 1) + the InstanceNorm statistics of its output (scale / shift / max /
     argmax from the epilogue partials) at W = 16, 32, 64, 128;
   * the data gradient onto the reflection-padded input (interior by the window pass, the padded
-    grid's ring by the rows pass, folded onto the border), with and without the residual addend;
+    grid's ring by ring16_kernel, folded onto the border), with and without the residual addend;
+  * the geometries dcs_conv3_win_ok rejects (W < 16; a data gradient that is not 256-channel) on the
+    rows pass they take, at the same bars;
   * equality of bar with the rows pass it replaces: the same fp32-class bound (max error / max |ref|
     <= 1e-5) and within 1.5x of the exact-f32 MFMA path's error.
 Tolerances written per check below."""
@@ -33,18 +35,26 @@ def ops():
     o._WIN = prev_win
 
 
+def _shapes(*shapes):
+    """(N, H, W[, C]) cases; C defaults to the model's 256 and is named in the id only where it differs."""
+    return [pytest.param(*s[:3], s[3] if len(s) > 3 else 256, id="-".join(map(str, s))) for s in shapes]
+
+
 def _geom(ops, cin=256, cout=256):
     from modules.hip.lib import DCS_PAD_REFLECT
     return ops.ConvGeom(cin, cout, 3, 1, (1, 1, 1, 1), DCS_PAD_REFLECT)
 
 
-@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 32, 32), (2, 16, 64), (1, 8, 128), (2, 32, 8)])
-def test_win_forward_and_stats_vs_fp64(ops, N, H, W):
+@pytest.mark.parametrize("N,H,W,C", _shapes((2, 16, 16), (1, 32, 32), (2, 16, 64), (1, 8, 128), (2, 32, 8),
+                                             (2, 16, 16, 128)))
+def test_win_forward_and_stats_vs_fp64(ops, N, H, W, C):
+    """(2, 32, 8): W < 16, the rows pass behind the window pack; C 128: the window kernel off the model's
+    channel count."""
     ops.set_mma("f16x3")
-    g = _geom(ops)
-    assert g.win
-    x = rnd((N, 256, H, W), 51, "x").double()
-    w = torch.from_numpy(prng.normal(52, "w", (256, 256, 3, 3), 0, 0.05)).float().double()
+    g = _geom(ops, C, C)
+    assert g.win  # (C % 32 == 0: holds for 128 as for 256)
+    x = rnd((N, C, H, W), 51, "x").double()
+    w = torch.from_numpy(prng.normal(52, "w", (C, C, 3, 3), 0, 0.05)).float().double()
     ref = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), w)
     mean = ref.mean(dim=(2, 3))
     var = ref.var(dim=(2, 3), unbiased=False)
@@ -66,18 +76,21 @@ def test_win_forward_and_stats_vs_fp64(ops, N, H, W):
 
 
 @pytest.mark.parametrize("addend", [False, True])
-@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 16, 128), (5, 32, 32), (3, 16, 64), (2, 8, 128), (2, 32, 8)])
-def test_win_dgrad_reflect_vs_fp64(ops, N, H, W, addend):
+@pytest.mark.parametrize("N,H,W,C", _shapes((2, 16, 16), (1, 16, 128), (5, 32, 32), (3, 16, 64), (2, 8, 128),
+                                             (2, 32, 8), (2, 16, 16, 128)))
+def test_win_dgrad_reflect_vs_fp64(ops, N, H, W, C, addend):
     """The reflect-pad data gradient: interior by the window kernel, the padded grid's ring by
     ring16_kernel (ring segments over the batch in 64-position tiles: the sizes here leave partial
-    tiles and tiles that straddle images), folded onto the border; against float64 at 1e-5."""
+    tiles and tiles that straddle images), folded onto the border; against float64 at 1e-5.
+    (2, 32, 8) and C 128 (the smallest shape that reaches the border fold with two images): geometries
+    dcs_conv3_win_ok rejects, on the rows pass with the fold in its epilogue (no addend) or after it."""
     ops.set_mma("f16x3")
-    g = _geom(ops)
-    x = rnd((N, 256, H, W), 61, "x").double().requires_grad_(True)
-    w = torch.from_numpy(prng.normal(62, "w", (256, 256, 3, 3), 0, 0.05)).float().double()
+    g = _geom(ops, C, C)
+    x = rnd((N, C, H, W), 61, "x").double().requires_grad_(True)
+    w = torch.from_numpy(prng.normal(62, "w", (C, C, 3, 3), 0, 0.05)).float().double()
     y = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), w)
     R = torch.from_numpy(prng.normal(63, "R", tuple(y.shape))).float().double()
-    A = rnd((N, 256, H, W), 64, "A").double() if addend else None
+    A = rnd((N, C, H, W), 64, "A").double() if addend else None
     (y * R).sum().backward()
     ref = x.grad + (A if addend else 0)
     Rd = R.float().to(DEV).permute(0, 2, 3, 1).contiguous()
@@ -114,13 +127,29 @@ def test_win_matches_rows_pass_error(ops):
 
 
 def test_win_ok_rejects_other_geometries(ops):
+    """dcs_conv3_win_ok is the one place that decides (host queries: no conv kernel runs)."""
     from modules.hip import lib
     ops.set_mma("f16x3")
-    g = _geom(ops)
-    x = torch.zeros(1, 9, 9, 256, device=DEV)  # 256 % 9 != 0: the rows pass keeps these
-    d = g._desc_fwd(ops.Src.nhwc(x), 2304, 0, 0)
-    ops._set_mma(d, x, None, torch.zeros(512, device=DEV))
-    assert lib.query("dcs_conv3_win_ok", ctypes.byref(d), 0) == 0
+
+    def fwd_ok(H, W, cin, cout=256):
+        g = _geom(ops, cin, cout)
+        x = torch.zeros(1, H, W, cin, device=DEV)
+        d = g._desc_fwd(ops.Src.nhwc(x), 9 * cin, 0, 0)
+        ops._set_mma(d, x, None, torch.zeros(512, device=DEV))
+        return lib.query("dcs_conv3_win_ok", ctypes.byref(d), 0)
+
+    def dgrad_ok(H, W, C):
+        g = _geom(ops, C, C)
+        dy = torch.zeros(1, H, W, C, device=DEV)
+        d = g._desc_dgrad(dy, g.pack_dgrad(torch.zeros(C, C, 3, 3, device=DEV)), C, H, W)
+        return lib.query("dcs_conv3_win_ok", ctypes.byref(d), 1)
+
+    assert fwd_ok(9, 9, 256) == 0    # 256 % 9 != 0: the rows pass keeps these
+    assert fwd_ok(32, 8, 256) == 0   # W < 16
+    assert fwd_ok(16, 16, 48) == 0   # Cs % 32 != 0
+    assert dgrad_ok(16, 16, 128) == 0  # the ring kernel is 256-channel
+    assert fwd_ok(16, 16, 256) == 1
+    assert dgrad_ok(16, 16, 256) == 1
 
 
 @pytest.mark.parametrize("N,H,W", [(2, 16, 64), (1, 20, 64), (1, 8, 128), (1, 32, 128)])
@@ -194,12 +223,14 @@ def test_win_wgrad_f16_vs_fp64(ops, N, H, W):
     assert torch.equal(dw, g.wgrad(Rd, ops.Src.nhwc(xd)))
 
 
-@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 16, 128)])
+@pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 16, 128), (2, 32, 8)])
 def test_win_dgrad_inbwd_matches_separate_pass(ops, N, H, W):
     """The InstanceNorm backward of a = relu(IN(y)) with its partial sums fused into the window data
     gradient that produces da (dcs_conv_dgrad_reflect_win_inbwd: tile epilogue + ring fold) against the
     separate partial-sum pass on the same da (dcs_in_act_backward): dx bit-identical (same kernels),
-    dy within 1e-5 of max |dy| (the sums run in a different order), and against float64."""
+    dy within 1e-5 of max |dy| (the sums run in a different order), and against float64.
+    (2, 32, 8): W < 16, no window kernel, so dgrad returns no partial sums and the separate pass is the
+    route; it meets the same float64 bar."""
     from modules.hip.lib import ACT_RELU
     ops.set_mma("f16x3")
     g = _geom(ops)
@@ -209,12 +240,16 @@ def test_win_dgrad_inbwd_matches_separate_pass(ops, N, H, W):
     R = torch.from_numpy(prng.normal(113, "R", (N, 256, H, W))).float().to(DEV).permute(0, 2, 3, 1).contiguous()
     wd = g.pack_dgrad(w)
     da_f, parts, nch = g.dgrad(R, wd, H, W, inbwd=(y, st, ACT_RELU))
-    assert parts is not None and nch == H * W // 256 + 64
-    dy_f = ops.in_act_backward_parts(da_f, y, st, ACT_RELU, parts, nch)
     da_s = g.dgrad(R, wd, H, W)
     assert torch.equal(da_f, da_s)
     dy_s = ops.in_act_backward(da_s, y, st, ACT_RELU)
-    assert _relmax(dy_f, dy_s.double().cpu()) <= 1e-5
+    if W >= 16:
+        assert parts is not None and nch == H * W // 256 + 64
+        dy_f = ops.in_act_backward_parts(da_f, y, st, ACT_RELU, parts, nch)
+        assert _relmax(dy_f, dy_s.double().cpu()) <= 1e-5
+    else:
+        assert parts is None and nch == 0
+        dy_f = dy_s
     # float64 IN backward of the same da
     yd = y.double().cpu().requires_grad_(True)
     m = yd.mean(dim=(1, 2), keepdim=True)
