@@ -226,6 +226,14 @@ SIGNATURES = {
     "dcs_nmodel_targets_workspace_size": (c_size_t, [c_int, c_int, c_int]),
     "dcs_nmodel_targets": (c_int, [P, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, c_size_t,
                                    P]),
+    "dcs_cc3_label": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "dcs_heart_workspace_size": (c_size_t, [c_int, c_int, c_int]),
+    "dcs_heart_modify": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_int, P, P,
+                                 c_size_t, P]),
+    "dcs_organ_mask_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dcs_organ_mask": (c_int, [P, c_int, c_int, c_int, POINTER(c_int32), c_int, P, c_int, P, c_int, c_int, P, P,
+                               c_size_t, P]),
+    "dcs_organ_apply": (c_int, [P, P, P, P, c_int64, c_int, P, P, P, P]),
 }
 
 

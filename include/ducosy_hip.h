@@ -930,6 +930,45 @@ int dcs_nmodel_targets(const void* ncct, int ncct_unsigned, const float* ncct_sl
                        const float* merged, int D, int H, int W, float threshold, float* vue_out, float* diff_out,
                        double* stats_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- heart-mask clean-up and organ masking (organ_masks.hip; modules/organ_masks.py is the
+ *      definition; reference modify_heart_mask.py:87-198, masking.py:455-541) ----
+ * Dense [D][H][W] uint8 label volumes, x fastest (a NIfTI file's own order: nibabel's [x, y, z] is
+ * x = W index, y = H index, z = D index).  Integer atomics only (min / max / add), so every result is
+ * order-independent and bit-identical from run to run, and equal to the host functions bit for bit.
+ * Arguments are checked on the host before any launch: DCS_E_INVALID for null pointers, an empty
+ * volume, D*H*W >= 2^31 or a label >= 256; DCS_E_WORKSPACE for a short workspace. */
+/* 3-D connected components of {vol == match}, 6-connectivity (scipy.ndimage.label's default
+ * structure up to renumbering).  labels[i]: the smallest voxel index of i's component, -1 for
+ * background.  At every root r (labels[r] == r): count[r] voxels; with sums and keys (both or
+ * neither) also sums[r], sums[np + r], sums[2 np + r] = the sums of the x, y, z coordinates and
+ * keys[r] = the minimum of (x * H + y) * D + z, the component's first voxel in [x, y, z] raster
+ * order.  Entries of count / sums / keys that are not at a root are left untouched. */
+int dcs_cc3_label(const uint8_t* vol, int match, int D, int H, int W, int32_t* labels, int32_t* count,
+                  int64_t* sums, uint32_t* keys, void* stream);
+/* bytes of workspace; 0 for dimensions the entry point refuses */
+size_t dcs_heart_workspace_size(int D, int H, int W);
+/* modules/organ_masks.py::modify_heart_label: the lowest heart component (centre z, ties by first
+ * voxel) is chosen on the device, the column gap cut, the float64 distance test (one rounding per
+ * numpy operation, offset_y_base_m1 = offset_y_base - 1 as the host computes it), the size filter
+ * and the write-back follow without a host wait.  out must not alias vol. */
+int dcs_heart_modify(const uint8_t* vol, int D, int H, int W, int heart_label, int gap_threshold, double offset,
+                     double offset_y_base_m1, double offset_z, int min_region, uint8_t* out, void* ws,
+                     size_t ws_bytes, void* stream);
+/* bytes of workspace for N slices handled `chunk` slices at a time (chunk * nlabels binary images
+ * of 5 bytes per pixel, plus N*H*W + 256 N); 0 for dimensions the entry point refuses
+ * (chunk * nlabels > 65535 or chunk * nlabels * (H*W + 4096) >= 2^31 among them) */
+size_t dcs_organ_mask_workspace_size(int N, int H, int W, int nlabels, int chunk);
+/* modules/organ_masks.py::organ_mask.  target: HOST array of nlabels labels (each < 256).
+ * brush1 / brush2: HOST arrays of (dy, dx) int8 pairs, 1..25 offsets within radius 2 (the
+ * thickness-2 and thickness-4 line brushes).  A (slice, label) pair the slice does not hold costs
+ * no pixel pass.  out: uint8 0/1 [N][H][W], must not alias labels. */
+int dcs_organ_mask(const uint8_t* labels, int N, int H, int W, const int32_t* target, int nlabels,
+                   const int8_t* brush1, int nbrush1, const int8_t* brush2, int nbrush2, int chunk, uint8_t* out,
+                   void* ws, size_t ws_bytes, void* stream);
+/* out_k[i] = mask[i] ? fill : k[i] for three int16 series of n values in one pass; no output may alias an input */
+int dcs_organ_apply(const int16_t* a, const int16_t* b, const int16_t* c, const uint8_t* mask, int64_t n, int fill,
+                    int16_t* out_a, int16_t* out_b, int16_t* out_c, void* stream);
+
 /* small utilities */
 int dcs_scale_add(float* y, const float* x, float a, int64_t n, void* stream); /* y += a*x */
 /* out = x * (*s) with s a device scalar (loss backward without a host sync) */
